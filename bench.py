@@ -1,6 +1,13 @@
 """Benchmark of the MVDet project+fuse hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure, its
+stage times and rooflines from the events inside those steps).  ``--full`` adds every leg that takes runs
+of its own: the CPU baselines, the other feature layout, the +a4 variant, the other configs, the training
+step, the other precision, the sustained-MFMA probe (N > 1: the other modes and the CPU baseline).
+``--dump-outputs DIR`` writes what the last timed step returned (the map, ``DIR/map_result.npy``, float32);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 A *step* is one pass of the hot path over one frame batch of synthetic input
 already resident in HBM: the warp of every view (a5), the zero-copy concat (a6),
@@ -31,7 +38,7 @@ FP32_MFMA_PEAK_TFS = 157.3  # MI355X_MICROARCH.md: fp32 matrix peak (spec)
 
 
 def progress(msg: str) -> None:
-    """A progress line on stderr (a long default run — the CPU baselines take minutes — keeps writing,
+    """A progress line on stderr (a long --full run — the CPU baselines take minutes — keeps writing,
     so a supervisor that watches the output does not take it for hung)."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
@@ -144,7 +151,23 @@ def mfma_probe(settle_s: float = 1.5):
     return v if v > 0 else None
 
 
-def run_single(args, precision, steps, warmup, with_cpu, config=None, cpu_plan=None, layout=None):
+OUTPUT_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outputs: dict, out_dir: Path) -> None:
+    """``--dump-outputs``: each array of ``outputs`` as ``out_dir/<name>.npy`` (float32); an array over its share
+    of the budget is cut to a fixed, seeded sample of its elements (flat, in index order)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = OUTPUT_BUDGET_BYTES // max(1, len(outputs)) // 4
+    for name, t in outputs.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(out_dir / f"{name}.npy", a)
+
+
+def run_single(args, precision, steps, warmup, with_cpu, config=None, cpu_plan=None, layout=None, outputs=None):
+    """``outputs``: a dict that receives what the last timed step returned (``map_result``)."""
     from mvdet_amd import ProjectFuse, synthetic
     from mvdet_amd.geometry import projection_matrices, touched_footprint
 
@@ -195,10 +218,12 @@ def run_single(args, precision, steps, warmup, with_cpu, config=None, cpu_plan=N
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(K):
-            step(i)
+            last = step(i)
             end_ev[i].record()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+    if outputs is not None:
+        outputs["map_result"] = last
 
     def avg(a, b):
         return float(np.mean([a[i].elapsed_time(b[i]) for i in range(K)]))
@@ -611,6 +636,13 @@ def main():
     ap.add_argument("--precision", default="bf16x3", choices=["fp32", "bf16x3"],
                     help="conv1/conv2 arithmetic: 3xbf16 split (default) or fp32-input MFMA")
     ap.add_argument("--config", type=int, default=2, help="BASELINE.json config index (1-based)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg that takes runs of its own (CPU baselines, the other layout / precision / "
+                         "configs, +a4, the training step, the MFMA probe; N>1: the other modes); the --no-* and "
+                         "--*-cfg options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/map_result.npy (float32; "
+                         "single GPU)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true", help="skip the sustained-MFMA-rate probe (roofline.sustained_peak)")
     ap.add_argument("--no-alt", action="store_true", help="skip the other-precision comparison line")
@@ -636,6 +668,13 @@ def main():
 
     if args.gpus < 1:
         sys.exit(f"bench.py: --gpus {args.gpus} < 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit(f"bench.py: --steps {args.steps} must be >= 1 and --warmup {args.warmup} >= 0")
+    if args.dump_outputs and args.gpus > 1:
+        sys.exit("bench.py: --dump-outputs writes the single-GPU path's map (--gpus 1)")
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_probe = args.no_alt = args.no_train = True
+        args.north_star_cfg = args.roofline_cfg = args.batch_cfg = 0
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -647,7 +686,11 @@ def main():
         from mvdet_amd import parallel
         return parallel.bench_main(args)
 
-    res = run_single(args, args.precision, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline and rank == 0)
+    outputs = {} if args.dump_outputs else None
+    res = run_single(args, args.precision, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline and rank == 0,
+                     outputs=outputs)
+    if outputs is not None:
+        dump_outputs(outputs, Path(args.dump_outputs))
     result = {
         "metric": "multi-view frames/sec (project+fuse)",
         "value": res["value"],
@@ -671,14 +714,14 @@ def main():
     }
     if result["cpu_baseline"]:
         result["speedup_vs_cpu"] = round(res["value"] / result["cpu_baseline"]["value"], 1)
-    if args.config != 4 and args.precision == "bf16x3":
+    if args.full and args.config != 4 and args.precision == "bf16x3":
         # the same step on the other feature memory format (channels-last: warp_wino_cl_kernel reads
         # one 128-B line per source pixel instead of NCHW's per-channel boxes)
         other_layout = "channels_last" if args.layout == "nchw" else "nchw"
         ol = run_single(args, args.precision, max(5, args.steps // 2), 2, with_cpu=False, layout=other_layout)
         result[other_layout] = {k: ol[k] for k in ("value", "ms_per_step", "stages_ms")}
         result[other_layout]["warp"] = ol["stage_roofline"]["warp"]
-    if args.config != 4:  # the fused upsample+warp writes fp32 / split slabs (not the fp16 slab)
+    if args.full and args.config != 4:  # the fused upsample+warp writes fp32 / split slabs (not the fp16 slab)
         result["plus_a4"] = run_plus_a4(args, args.precision, max(5, args.steps // 2), 2)
     subs = []
     if args.north_star_cfg and args.north_star_cfg != args.config:

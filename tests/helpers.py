@@ -16,7 +16,19 @@ ATOL_FRAC = 1e-3
 
 
 def load_golden(name):
+    """``golden/<name>.npz`` and the arrays kept in files of their own (no fixture file passes 1 MiB):
+    ``<name>.<key>.npz`` holds the whole array, ``<name>.<key>.v<i>.npz`` its view i (axis 1)."""
     d = dict(np.load(GOLDEN / f"{name}.npz", allow_pickle=False))
+    views = {}
+    for p in GOLDEN.glob(f"{name}.*.npz"):
+        key, *view = p.name[len(name) + 1:-len(".npz")].split(".")
+        a = np.load(p, allow_pickle=False)[key]
+        if view:
+            views.setdefault(key, {})[int(view[0][1:])] = a
+        else:
+            d[key] = a
+    for key, parts in views.items():
+        d[key] = np.stack([parts[i] for i in range(len(parts))], 1)
     if "meta" in d:
         d["meta"] = json.loads(str(d["meta"]))
     return d

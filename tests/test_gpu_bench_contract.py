@@ -1,5 +1,6 @@
 """bench.py's one-line JSON contract on a small config (cfg1, 2 steps): the keys the driver and
-the judge read, a roofline whose fraction is achieved / peak, and a CPU baseline that ran."""
+the judge read, a roofline whose fraction is achieved / peak, and (``--full``) a CPU baseline that ran;
+a plain run carries the headline only and ``--dump-outputs`` writes its map."""
 from __future__ import annotations
 
 import json
@@ -16,9 +17,9 @@ ROOT = Path(__file__).resolve().parents[1]
 @pytest.mark.gpu
 def test_bench_json_line_contract():
     env = dict(os.environ, PYTHONUNBUFFERED="1")
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", "1", "--steps", "2", "--warmup", "1",
-                          "--no-train", "--no-alt", "--cpu-frames", "1", "--north-star-cfg", "2", "--roofline-cfg", "0",
-                          "--batch-cfg", "0"],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--config", "1", "--steps", "2",
+                          "--warmup", "1", "--no-train", "--no-alt", "--cpu-frames", "1", "--north-star-cfg", "2",
+                          "--roofline-cfg", "0", "--batch-cfg", "0"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -56,6 +57,32 @@ def test_bench_json_line_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_map(tmp_path):
+    """Without ``--full`` the run times its steps and nothing else (no CPU baseline, no other layout /
+    precision / config, no training step), and ``--dump-outputs`` writes the last timed step's map."""
+    import numpy as np
+    env = dict(os.environ, PYTHONUNBUFFERED="1")
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--config", "1", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
+                         cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["metric"] == "multi-view frames/sec (project+fuse)" and r["unit"] == "frames/s"
+    assert r["higher_is_better"] is True and r["dtype"].startswith("f32")
+    assert r["n_gpus"] == 1 and r["steps"] == 3 and r["warmup"] == 1
+    assert r["value"] > 0 and abs(r["value"] * r["ms_per_step"] / 1e3 - 1.0) < 0.05  # B = 1 at cfg1
+    assert r["cpu_baseline"] is None and r["roofline"]["sustained_peak"] is None
+    for leg in ("speedup_vs_cpu", "channels_last", "plus_a4", "cfg3", "cfg4", "cfg5", "train_step", "alt_precision"):
+        assert leg not in r, leg
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["map_result.npy"]
+    m = np.load(tmp_path / "dump" / "map_result.npy")
+    assert m.dtype == np.float32 and m.shape == (r["config"]["batch"], 1, *r["config"]["grid_hw"])
+    assert np.isfinite(m).all() and np.abs(m).max() > 0
+
+
+@pytest.mark.gpu
 def test_bench_multi_rank_json_line():
     """The N > 1 path as the driver launches it (torch.distributed.run, one JSON line from rank 0),
     rehearsed with 2 gloo ranks sharing the box's one GPU: the view-parallel band exchange as
@@ -68,7 +95,8 @@ def test_bench_multi_rank_json_line():
     env = dict(os.environ, PYTHONUNBUFFERED="1", MVBEV_DIST_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"),
-                          "--gpus", "2", "--config", "1", "--steps", "2", "--warmup", "1", "--north-star-cfg", "0"],
+                          "--gpus", "2", "--full", "--config", "1", "--steps", "2", "--warmup", "1",
+                          "--north-star-cfg", "0"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -104,8 +132,8 @@ def test_bench_gpus_flag_spawns_ranks_without_a_launcher():
     two ranks itself (gloo, sharing the one GPU of the test box) and the line says n_gpus 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["PYTHONUNBUFFERED"] = "1"
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--config", "1", "--steps", "2",
-                          "--warmup", "1", "--north-star-cfg", "0", "--no-alt"],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--config", "1",
+                          "--steps", "2", "--warmup", "1", "--north-star-cfg", "0", "--no-alt"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

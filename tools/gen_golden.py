@@ -49,6 +49,19 @@ def _meta(ds, **extra):
     return json.dumps(d)
 
 
+def save_fixture(name, arrays, own_file=(), per_view=()):
+    """``tests/golden/<name>.npz`` plus, so that no fixture file passes 1 MiB, the arrays named in ``own_file``
+    as ``<name>.<key>.npz`` and those in ``per_view`` ([B, N, ...]) as ``<name>.<key>.v<i>.npz``, one per view
+    (``tests/helpers.py::load_golden`` puts them back together)."""
+    main = {k: v for k, v in arrays.items() if k not in own_file and k not in per_view}
+    np.savez_compressed(OUT / f"{name}.npz", **main)
+    for k in own_file:
+        np.savez_compressed(OUT / f"{name}.{k}.npz", **{k: arrays[k]})
+    for k in per_view:
+        for i in range(arrays[k].shape[1]):
+            np.savez_compressed(OUT / f"{name}.{k}.v{i}.npz", **{k: arrays[k][:, i]})
+
+
 def run_module_case(name, ds, B, backbone_hw, wseed, fseed, store_full):
     P = load_reference_detector()
     torch.manual_seed(0)
@@ -102,7 +115,8 @@ def run_module_case(name, ds, B, backbone_hw, wseed, fseed, store_full):
     )
     if store_full:
         arrays.update(warp_out=warp_out, conv1_relu=acts["c1"].numpy(), conv2_relu=acts["c2"].numpy())
-    np.savez_compressed(OUT / f"{name}.npz", **arrays)
+    save_fixture(name, arrays, own_file=("conv1_relu", "conv2_relu") if store_full else (),
+                 per_view=("warp_out",) if store_full else ())
     print(name, {k: v.shape for k, v in arrays.items()}, "map max", float(np.abs(arrays["map_result"]).max()))
 
 

@@ -784,6 +784,66 @@ int mvbev_point_nms_ws(const float* points, const float* scores, int64_t K, floa
                        int64_t top_k, int64_t* keep, int32_t* count, void* workspace, size_t ws_bytes,
                        void* stream);
 
+/* ---- training criterion (multiview_detector/loss/gaussian_mse.py:7-20, trainer.py:43-56) ----
+ * Added after 12400 (mvbev_version() stays 12400): mvbev_adaptive_max_pool_f32,
+ * mvbev_gaussian_mse_blocks, mvbev_gaussian_mse_f32, mvbev_loss_finalize_f32,
+ * mvbev_gaussian_mse_backward_f32.  All fp32, on the caller's stream, caller-owned buffers, no host
+ * sync.  One launch covers a host array of n (<= 16) items; an item is one (prediction, target)
+ * pair of mse_loss(x, conv2d(adaptive_max_pool2d(target, x.shape[2:]), kernel, padding=(k-1)/2)). */
+typedef struct mvbev_loss_item {
+  const float* x;        /* prediction [B][C][h][w], element strides x_strides (any, >= 0); NULL:
+                          * only the transformed target is wanted (diff must be NULL too) */
+  int64_t x_strides[4];
+  const float* target;   /* ground truth [B][C][Ht][Wt], element strides t_strides (any, >= 0) */
+  int64_t t_strides[4];
+  int64_t C, h, w, Ht, Wt;
+  float* pooled;         /* [B][C][h][w] contiguous scratch; unused (may be NULL) when Ht == h && Wt == w */
+  float* t_out;          /* optional: the transformed target, [B][C][h][w] contiguous */
+  float* diff;           /* optional: x - t, [B][C][h][w] contiguous, kept for the backward */
+  int32_t kernel_id;     /* index into the kernels array of mvbev_gaussian_mse_f32 */
+  float weight;          /* this item's factor in the total loss (1, or alpha / N) */
+} mvbev_loss_item;
+
+/* One uploaded [C][C][k][k] kernel and its host-side plan (made once per kernel version). */
+typedef struct mvbev_loss_kernel {
+  const float* w;        /* device, contiguous [C][C][k][k] */
+  int64_t C, k;          /* C <= 8, k odd */
+  uint64_t slice_mask;   /* bit co * C + ci set: slice (co, ci) holds a non-zero (or non-finite) value */
+  int32_t finite;        /* every value is finite: the two exact skips (all-zero slice, all-zero
+                          * staged target) apply; 0: every tap is multiplied with every target cell
+                          * inside the image, so 0 * NaN reaches t (the padding is never multiplied,
+                          * as in torch's conv2d) */
+} mvbev_loss_kernel;
+
+/* F.adaptive_max_pool2d(target, (h, w)) into pooled for every item whose sizes differ (the others
+ * are skipped): window rows floor(i Ht / h) .. ceil((i + 1) Ht / h), columns alike; NaN wins. */
+int mvbev_adaptive_max_pool_f32(const mvbev_loss_item* items, int n, int64_t B, void* stream);
+
+/* Workgroups of mvbev_gaussian_mse_f32 over these items = rows of its partials (0: invalid). */
+int64_t mvbev_gaussian_mse_blocks(const mvbev_loss_item* items, int n, int64_t B);
+
+/* Per 16 x 64 output tile: the (pooled) target tile plus its (k-1)/2 halo staged into LDS (zeros
+ * outside the image), the direct C x C x k x k convolution, d = x - t, t_out / diff when asked,
+ * and one row of partials per workgroup: partials[4 g] = sum d^2, [4 g + 1] = #(x > cls_thres and
+ * gt == 1), [4 g + 2] = #(x > cls_thres), [4 g + 3] = sum gt — the last three only for item
+ * stats_item (-1: none; its target must have x's size), 0 elsewhere.  partials: device fp64,
+ * >= 4 * mvbev_gaussian_mse_blocks values.  MVBEV_ERR_SHAPE: even k, C > 8, a kernel whose C
+ * differs from the item's, or a tile C (15 + k) (63 + k) floats that does not fit 64 KiB of LDS.
+ * No atomics on floats: bitwise repeatable. */
+int mvbev_gaussian_mse_f32(const mvbev_loss_item* items, int n, int64_t B, const mvbev_loss_kernel* kernels,
+                           int nkernels, float cls_thres, int stats_item, double* partials, int64_t npartials,
+                           void* stream);
+
+/* Sums the partials in a fixed order in fp64: *loss = sum_i weight_i sse_i / (B C_i h_i w_i)
+ * (fp32); stats (optional, fp64[3]) = tp, fp = pred - tp, fn = gt_sum - tp of item stats_item. */
+int mvbev_loss_finalize_f32(const mvbev_loss_item* items, int n, int64_t B, const double* partials,
+                            int64_t npartials, int stats_item, float* loss, double* stats, void* stream);
+
+/* grads[i] ([B][C][h][w] contiguous) = *grad_out * weight_i * 2 / numel_i * items[i].diff;
+ * grad_out is a device scalar (no sync).  grads: host array of n device pointers. */
+int mvbev_gaussian_mse_backward_f32(const mvbev_loss_item* items, int n, int64_t B, const float* grad_out,
+                                    float* const* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

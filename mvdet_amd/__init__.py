@@ -8,6 +8,9 @@ Public surface (mirrors the reference's):
 * ``ProjectFuse`` — the hot path (warp + zero-copy concat + fusion) as an engine.
 * ``postprocess.nms`` / ``threshold_rows`` / ``frame_results`` — drop-ins for
   ``multiview_detector.utils.nms.nms`` and the evaluation rows of ``trainer.py:97-157``.
+* ``GaussianMSE`` / ``detection_loss`` / ``gaussian_kernels`` — drop-ins for
+  ``multiview_detector.loss.gaussian_mse.GaussianMSE`` and the loss / precision-recall lines of
+  ``trainer.py:43-56`` (``mvdet_amd.loss``).
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -16,5 +19,8 @@ from .detector import PerspTransDetector  # noqa: F401
 from .ops import warp_perspective  # noqa: F401
 from .pipeline import ProjectFuse  # noqa: F401
 from . import postprocess  # noqa: F401
+from . import loss  # noqa: F401
+from .loss import GaussianMSE, detection_loss, gaussian_kernels  # noqa: F401
 
-__all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess"]
+__all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
+           "detection_loss", "gaussian_kernels"]

@@ -100,6 +100,12 @@ EXPORTS = (
     "mvbev_wino43_rows_split_bf16",
     "mvbev_conv3x3_wino43_bf16x3",
     "mvbev_conv3x3_wino43_bf16x3_cout1_partials",
+    # the training criterion (added after 12400; the version stays 12400)
+    "mvbev_adaptive_max_pool_f32",
+    "mvbev_gaussian_mse_blocks",
+    "mvbev_gaussian_mse_f32",
+    "mvbev_loss_finalize_f32",
+    "mvbev_gaussian_mse_backward_f32",
 )
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
 BEV_SRC_CHANNELS_LAST = 16  # MVBEV_BEV_SRC_CHANNELS_LAST (flag)
@@ -163,6 +169,21 @@ class BevPlan(ctypes.Structure):
                 ("Cs", ctypes.c_int64), ("tiles", ctypes.c_int64), ("off", ctypes.c_size_t * 24),
                 ("workspace_bytes", ctypes.c_size_t),
                 ("b2", ctypes.c_void_p), ("w3", ctypes.c_void_p)]
+
+
+class LossItem(ctypes.Structure):
+    """``mvbev_loss_item`` (include/mvbev.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_strides", ctypes.c_int64 * 4), ("target", ctypes.c_void_p),
+                ("t_strides", ctypes.c_int64 * 4)] + \
+        [(n, ctypes.c_int64) for n in ("C", "h", "w", "Ht", "Wt")] + \
+        [("pooled", ctypes.c_void_p), ("t_out", ctypes.c_void_p), ("diff", ctypes.c_void_p),
+         ("kernel_id", ctypes.c_int32), ("weight", ctypes.c_float)]
+
+
+class LossKernel(ctypes.Structure):
+    """``mvbev_loss_kernel`` (include/mvbev.h)."""
+    _fields_ = [("w", ctypes.c_void_p), ("C", ctypes.c_int64), ("k", ctypes.c_int64),
+                ("slice_mask", ctypes.c_uint64), ("finite", ctypes.c_int32)]
 
 
 class NativeError(RuntimeError):
@@ -386,6 +407,18 @@ def _declare(lib):
     lib.mvbev_relu_backward_split_f32.argtypes = [_p, _p, _i64, _i64, _i64, _i64, _p, _p]
     lib.mvbev_cout1_reduce_partials.restype = ctypes.c_int
     lib.mvbev_cout1_reduce_partials.argtypes = [_p, ctypes.POINTER(ConvDesc), _i64, ctypes.c_int, _p, _i64, _i64, _p]
+    items = ctypes.POINTER(LossItem)
+    lib.mvbev_adaptive_max_pool_f32.restype = ctypes.c_int
+    lib.mvbev_adaptive_max_pool_f32.argtypes = [items, ctypes.c_int, _i64, _p]
+    lib.mvbev_gaussian_mse_blocks.restype = _i64
+    lib.mvbev_gaussian_mse_blocks.argtypes = [items, ctypes.c_int, _i64]
+    lib.mvbev_gaussian_mse_f32.restype = ctypes.c_int
+    lib.mvbev_gaussian_mse_f32.argtypes = [items, ctypes.c_int, _i64, ctypes.POINTER(LossKernel), ctypes.c_int,
+                                           ctypes.c_float, ctypes.c_int, _p, _i64, _p]
+    lib.mvbev_loss_finalize_f32.restype = ctypes.c_int
+    lib.mvbev_loss_finalize_f32.argtypes = [items, ctypes.c_int, _i64, _p, _i64, ctypes.c_int, _p, _p, _p]
+    lib.mvbev_gaussian_mse_backward_f32.restype = ctypes.c_int
+    lib.mvbev_gaussian_mse_backward_f32.argtypes = [items, ctypes.c_int, _i64, _p, ctypes.POINTER(ctypes.c_void_p), _p]
 
 
 def load(path: os.PathLike | str | None = None):

@@ -744,9 +744,10 @@ int mvbev_conv3x3_bias_coord_grad_f32(const float* dy, int64_t B, int64_t Cout, 
                                       int dilation, float* db, float* dw, int64_t Cin_w,
                                       int64_t coord_ch, void* stream);
 
-/* In place: dy[i] = y[i] > 0 ? dy[i] : 0 (y = the ReLU's output; torch threshold_backward). */
+/* In place: dy[i] = y[i] <= 0 ? 0 : dy[i] (y = the ReLU's output; torch threshold_backward: the gradient
+ * passes where y is NaN). */
 int mvbev_relu_backward_f32(float* dy, const float* y, int64_t n, void* stream);
-/* Same with y in the split-bf16 layout (y = hi + lo; [B][C/8][H][W] pieces, C % 8 == 0) and
+/* Same (NaN rule included) with y in the split-bf16 layout (y = hi + lo; [B][C/8][H][W] pieces, C % 8 == 0) and
  * dy fp32 [B][C][H][W]; dy_split (optional, 16-B aligned) also receives the masked dy in the
  * split layout (the next data-gradient conv's input). */
 int mvbev_relu_backward_split_f32(float* dy, const void* y_split, int64_t B, int64_t C, int64_t H, int64_t W,
@@ -754,7 +755,8 @@ int mvbev_relu_backward_split_f32(float* dy, const void* y_split, int64_t B, int
 
 /* Backward of mvbev_conv3x3_cout1_f32 over a whole image (x [B][C][H][W], w [C][3][3], dmap
  * [B][1][H][W] fp32):  dx[b][c][p] = sum_t w[c][t] dmap[b][p - s_t], zeroed where x <= 0 when
- * relu_mask (x is the previous ReLU's output: its backward fused); dw[c][t] = sum_b,p
+ * relu_mask (x is the previous ReLU's output: its backward fused, torch threshold_backward, so dx passes
+ * where x is NaN); dw[c][t] = sum_b,p
  * dmap[b][p] x[b][c][p + s_t].  Any output may be NULL; dx_split (C % 8 == 0, 16-B aligned): dx
  * also in the split-bf16 layout ([B][C/8][H][W] pieces of bf16 hi[8], lo[8]), the input of the
  * next data-gradient conv. */

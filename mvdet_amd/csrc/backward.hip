@@ -11,7 +11,8 @@
 //                                            (mvbev_pack_conv3x3_dgrad_bf16x3, conv_bf16x3.hip);
 //                                            bias + coord-channel gradients: bias_coord_grad_kernel
 //   ReLUs (map_classifier[1], [3])          relu_backward_kernel (torch threshold_backward:
-//                                            grad where the ReLU output > 0)
+//                                            0 where the ReLU output <= 0, else grad: a NaN
+//                                            output passes its gradient)
 //   conv3 (map_classifier[4], Cout = 1)     cout1_dgrad_kernel (fused with conv2's ReLU mask),
 //                                            cout1_wgrad_kernel
 //
@@ -855,7 +856,8 @@ __global__ __launch_bounds__(kRedThreads) void bias_coord_grad_kernel(const floa
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
             const int xx = x + (k - 1) * dil;
-            const bool okx = xx >= 0 && xx < W;
+            // x < W: a lane past the row's end has no term either (its 0 times a NaN coord, W == 1, is NaN)
+            const bool okx = x < W && xx >= 0 && xx < W;
             rx[k] += okx ? gv[u] * tcx[okx ? xx : 0] : 0.f;
             sx[k] += okx ? gv[u] : 0.f;
           }
@@ -877,7 +879,8 @@ __global__ __launch_bounds__(kRedThreads) void bias_coord_grad_kernel(const floa
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
           v[1 + 3 * ky + kx] += oky ? rx[kx] : 0.f;
-          v[10 + 3 * ky + kx] += cy * sx[kx];
+          // a column tap with no pixel inside (dil >= W) has no term: exactly 0, also where cy is NaN (H == 1)
+          v[10 + 3 * ky + kx] += (oky && (kx == 1 || dil < W)) ? cy * sx[kx] : 0.f;
         }
       }
     }
@@ -898,21 +901,22 @@ __global__ __launch_bounds__(kRedThreads) void bias_coord_grad_kernel(const floa
   }
 }
 
-// torch threshold_backward(grad, relu_output, 0): grad where the ReLU output > 0, else 0
+// torch threshold_backward(grad, relu_output, 0): 0 where the ReLU output <= 0, else grad (so a NaN
+// output passes its gradient: !(y <= 0), not y > 0)
 __global__ void relu_backward_kernel(float* __restrict__ dy, const float* __restrict__ y, int64_t n) {
   const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 4;
   if (i + 4 <= n) {
     floatx4 g = *reinterpret_cast<const floatx4*>(dy + i);
     const floatx4 v = *reinterpret_cast<const floatx4*>(y + i);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) g[j] = v[j] > 0.f ? g[j] : 0.f;
+    for (int j = 0; j < 4; ++j) g[j] = !(v[j] <= 0.f) ? g[j] : 0.f;
     *reinterpret_cast<floatx4*>(dy + i) = g;
   } else {
-    for (int64_t j = i; j < n; ++j) dy[j] = y[j] > 0.f ? dy[j] : 0.f;
+    for (int64_t j = i; j < n; ++j) dy[j] = !(y[j] <= 0.f) ? dy[j] : 0.f;
   }
 }
 
-// dy (fp32 [B][C][HW]) *= [y > 0] with the ReLU output y in the split-bf16 layout
+// dy (fp32 [B][C][HW]) *= [!(y <= 0)] (threshold_backward: NaN passes) with the ReLU output y in the split-bf16 layout
 // ([B][C/8][HW] pieces of bf16 hi[8], lo[8]; y = hi + lo); dys (optional) also receives the
 // masked dy in the split layout, the input of the next data-gradient conv (ring kernel).
 __global__ void relu_backward_split_kernel(float* __restrict__ dy, const u32x4_t* __restrict__ y, int C, int64_t HW,
@@ -927,13 +931,14 @@ __global__ void relu_backward_split_kernel(float* __restrict__ dy, const u32x4_t
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     const float yv = (float)hi[c] + (float)lo[c];
-    v[c] = yv > 0.f ? d[c * HW] : 0.f;
+    v[c] = !(yv <= 0.f) ? d[c * HW] : 0.f;
     d[c * HW] = v[c];
   }
   if (dys) store_split8(dys + 2 * e, v);
 }
 
-// conv3 (Cout = 1, no bias) data gradient, times conv2's ReLU mask when relu_mask:
+// conv3 (Cout = 1, no bias) data gradient, times conv2's ReLU mask when relu_mask (threshold_backward on
+// x: zero where x <= 0, a NaN x passes):
 // dx[b][c][y][x] = sum_t w[c][t] * dmap[b][y - (ky-1)d][x - (kx-1)d]
 constexpr int kCout1Cpb = 32;  // channels per block
 // dxs (optional, C % 8 == 0): dx also in the split-bf16 layout (the next dgrad conv's input)
@@ -964,7 +969,7 @@ __global__ __launch_bounds__(256) void cout1_dgrad_kernel(const float* __restric
 #pragma unroll
         for (int t = 0; t < 9; ++t) s += w[c * 9 + t] * dm[t];
         const int64_t o = ((int64_t)b * C + c) * HW + q;
-        v[j] = (!relu_mask || x[o] > 0.f) ? s : 0.f;
+        v[j] = (!relu_mask || !(x[o] <= 0.f)) ? s : 0.f;
         dx[o] = v[j];
       }
       store_split8(dxs + 2 * (((int64_t)b * (C / 8) + c0 / 8) * HW + q), v);
@@ -976,7 +981,7 @@ __global__ __launch_bounds__(256) void cout1_dgrad_kernel(const float* __restric
 #pragma unroll
     for (int t = 0; t < 9; ++t) s += w[c * 9 + t] * dm[t];
     const int64_t o = ((int64_t)b * C + c) * HW + q;
-    dx[o] = (!relu_mask || x[o] > 0.f) ? s : 0.f;
+    dx[o] = (!relu_mask || !(x[o] <= 0.f)) ? s : 0.f;
   }
 }
 
@@ -1015,6 +1020,30 @@ __global__ __launch_bounds__(kRedThreads) void cout1_wgrad_kernel(const float* _
       for (int u = 0; u < kC1U; ++u)
 #pragma unroll
         for (int t = 0; t < 9; ++t) v[t] += xv[u] * dv[u][t];
+    }
+  }
+  // A tap that falls outside the map has no term — not the x * 0 of the loop above, which is NaN at a NaN / inf
+  // x: torch's zero padding keeps such an x near the border out of those taps.  A thread that met a non-finite x
+  // knows it from its centre tap (always inside: x * dmap is then inf or NaN and stays so), and sums its pixels
+  // (q = its index mod 1024, as above) again with the bounds as branches; off the hot path, a wave-uniform test.
+  if (__any(!isfinite(v[4]))) {
+    const int n = isfinite(v[4]) ? 0 : HW;
+    if (n)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) v[t] = 0.f;
+    for (int b = 0; b < B; ++b) {
+      const float* xc = x + ((int64_t)b * C + c) * HW;
+      const float* d = dmap + (int64_t)b * HW;
+#pragma unroll 1
+      for (int q = threadIdx.x; q < n; q += kRedThreads) {
+        const float xq = xc[q];
+        const int y = q / W, xx = q - y * W;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          const int yy = y - (t / 3 - 1) * dil, xs = xx - (t % 3 - 1) * dil;
+          if (yy >= 0 && yy < H && xs >= 0 && xs < W) v[t] += xq * d[yy * W + xs];
+        }
+      }
     }
   }
   block_sum<9, kRedWaves>(v, red);

@@ -703,8 +703,9 @@ __global__ __launch_bounds__(256) void zero_gated_kernel(u32x4_t* dst, int64_t n
 // a gated store (ABI 12200): fp32 src [B][C][H][W] (element strides) into dst as fp32 (element strides) or
 // as the split-bf16 blocked layout (32-B units: batch, channel group, row; 8 channels of a pixel per entry),
 // when *gate == tag — the training forward's exact path puts its activations where the native backward
-// reads them.  The split keeps a non-finite value in hi with lo = 0 (hi + lo is the value: inf stays inf,
-// so the backward's ReLU mask hi + lo > 0 is torch's), unlike the fast path's split (lo = v - hi).
+// reads them.  The split keeps a non-finite value in hi with lo = 0 (hi + lo is the value: inf stays inf and
+// NaN stays NaN, so the backward's ReLU mask !(hi + lo <= 0) is torch's threshold_backward: +inf and NaN pass
+// the gradient, -inf does not), unlike the fast path's split (lo = v - hi: NaN for an infinite v).
 struct StoreArgs {
   const float* src;
   int64_t sB, sC, sH;

@@ -1725,7 +1725,8 @@ def conv3x3_bias_coord_grad(dy: torch.Tensor, dilation: int, db: Optional[torch.
 
 
 def relu_backward_(dy: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-    """In place: dy = dy where y > 0 else 0 (``y`` = the ReLU's output)."""
+    """In place: dy = 0 where y <= 0 else dy (``y`` = the ReLU's output; torch's ``threshold_backward``:
+    the gradient passes where y is NaN)."""
     _require_cuda(dy, y)
     if dy.shape != y.shape or dy.dtype != torch.float32 or y.dtype != torch.float32 or \
             not dy.is_contiguous() or not y.is_contiguous():
@@ -1736,7 +1737,7 @@ def relu_backward_(dy: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 
 
 def relu_backward_split_(dy: torch.Tensor, y_split: torch.Tensor, dy_split: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """In place: dy [B,C,H,W] fp32 = dy where y > 0 else 0, with the ReLU output ``y_split`` in
+    """In place: dy [B,C,H,W] fp32 = 0 where y <= 0 else dy (NaN passes), with the ReLU output ``y_split`` in
     the split-bf16 layout (``split_shape(B, C, H, W)``, y = hi + lo); ``dy_split`` (optional,
     same split shape) also receives the masked dy in the split layout."""
     _require_cuda(dy, y_split)
@@ -1758,7 +1759,7 @@ def conv3x3_cout1_backward(x: torch.Tensor, weight: torch.Tensor, dmap: torch.Te
                            dx_split: Optional[torch.Tensor] = None):
     """Backward of ``conv3x3_cout1`` over a whole image: returns (dx [B,C,H,W] or None,
     dw [1,C,3,3] or None).  ``relu_mask``: zero dx where x <= 0 (x = the previous ReLU's output,
-    its backward fused).  ``dx_split`` (optional, bf16 ``split_shape(B,C,H,W)``) also receives
+    its backward fused; dx passes where x is NaN, as torch's ``threshold_backward``).  ``dx_split`` (optional, bf16 ``split_shape(B,C,H,W)``) also receives
     dx in the split-bf16 layout (the next data-gradient conv's input)."""
     _require_cuda(x, weight, dmap)
     if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():

@@ -65,6 +65,18 @@ def assert_parity(got, ref, what="", normwise_tol=1e-3):
     return s
 
 
+def masked_relu(pre, m):
+    """torch's ReLU with the sign decision of a given 0/1 pattern ``m`` where ``pre`` is not NaN (the GPU's
+    activation pattern: a pre-activation within fp32 rounding of 0 may fall either way): value
+    where(m, pre, 0) with NaN kept as NaN (and -0.0 kept as -0.0, as torch's clamp does); gradient 1 where
+    m or where ``pre`` is NaN, 0 elsewhere — ``nn.ReLU``'s backward is ``threshold_backward``,
+    ``y <= 0 ? 0 : grad``, which passes the gradient at a NaN output.  With m = (pre > 0) it is ``F.relu``
+    bit for bit, value and gradient (``test_oracle.py::test_masked_relu_is_torch_relu_nan_included``)."""
+    p = pre.detach()
+    off = torch.where(p == 0, p, torch.zeros_like(p))  # no gradient here; a signed zero keeps its sign
+    return torch.where((m > 0) | torch.isnan(p), pre, off)
+
+
 def parity_stats_t(got: torch.Tensor, ref: torch.Tensor, chunk: int = 1 << 26):
     """``parity_stats`` on torch tensors where they live (e.g. the GPU: full-size configs hold
     GB-sized tensors), in float64 chunks; the same gate and NaN/inf rule."""

@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn as nn
 
-from helpers import assert_parity_t
+from helpers import assert_parity_t, masked_relu
 from oracle import cpu_path, fixtures
 
 pytestmark = pytest.mark.gpu
@@ -175,22 +175,15 @@ def test_nonfinite_guard_two_warp_calls_one_frame_and_row_bands():
     assert_parity_t(got, ref, "two warp calls, banded exact path (NaN / inf pattern included)")
 
 
-def _masked_relu(pre, m):
-    """torch's ReLU with the sign decision of a given 0/1 pattern ``m`` where ``pre`` is not NaN (the GPU's
-    activation pattern: a pre-activation within fp32 rounding of 0 may fall either way): value
-    where(m, pre, 0), NaN kept as NaN, gradient 1 where m and 0 elsewhere (torch: grad * (y > 0))."""
-    nan = torch.where(torch.isnan(pre.detach()), pre.detach(), torch.zeros_like(pre))
-    return torch.where(m > 0, pre, torch.zeros_like(pre)) + nan
-
-
 @pytest.mark.parametrize("backbone", [False, True])
 def test_training_step_nonfinite_features_vs_cpu_autograd(backbone):
     """VERDICT r05 missing 2: a training step (``autograd.project_fuse`` / ``project_fuse_backbone``: the fused
     warp + B^T, Winograd convs, native backward) on features holding +inf / NaN / -inf.  The training forward's
     gated exact path (``ProjectFuse._train_exact``) rewrites the map AND stores the exact activations the native
     backward reads, so: the map has the reference's NaN / inf pattern; the feature gradients and the biases'
-    (finite in the reference: torch's ReLU backward passes no gradient through a NaN) pass the gate; conv2's
-    and conv3's weight gradients are NaN exactly where the reference's are (everywhere); conv1's weight
+    (finite in the reference: torch's ReLU backward, ``threshold_backward``, DOES pass the gradient at a NaN
+    activation — ``helpers.masked_relu`` — but the gradient arriving there is a finite conv data gradient) pass
+    the gate; conv2's and conv3's weight gradients are NaN exactly where the reference's are (everywhere); conv1's weight
     gradient is non-finite exactly in the reference's entries (the poisoned channels' columns; the row-Winograd
     form's B^T turns more of those infinities into NaN than the direct sum does) and equal elsewhere."""
     import torch.nn.functional as F
@@ -232,15 +225,16 @@ def test_training_step_nonfinite_features_vs_cpu_autograd(backbone):
     warped = cpu_path.warp_views(src, [M.numpy() for M in pm], grid)
     x = torch.cat(warped + [cpu_path.coord_map(*grid).repeat([B, 1, 1, 1])], 1)
     pre1 = F.conv2d(x, pr["map_classifier.0.weight"], pr["map_classifier.0.bias"], padding=1)
-    pre2 = F.conv2d(_masked_relu(pre1, m1), pr["map_classifier.2.weight"], pr["map_classifier.2.bias"], padding=2,
+    pre2 = F.conv2d(masked_relu(pre1, m1), pr["map_classifier.2.weight"], pr["map_classifier.2.bias"], padding=2,
                     dilation=2)
-    ref = F.conv2d(_masked_relu(pre2, m2), pr["map_classifier.4.weight"], None, padding=4, dilation=4)
+    ref = F.conv2d(masked_relu(pre2, m2), pr["map_classifier.4.weight"], None, padding=4, dilation=4)
     for m, pre in ((m1, pre1), (m2, pre2)):  # the GPU's pattern is torch's up to fp32 rounding near 0
         fin = torch.isfinite(pre)
         flip = (m != (pre > 0).float()) & fin
         assert flip.sum().item() <= max(2, pre.numel() // 20000)
         assert (pre[flip].abs() <= 1e-4 * pre[fin].abs().max()).all()
-        assert torch.equal(m[~fin].bool(), (pre[~fin] > 0))  # +inf passes, -inf / NaN do not
+        assert torch.equal(m[~fin].bool(), (pre[~fin] > 0))  # the pattern: 1 at +inf, 0 at -inf / NaN (whose gradient
+        # passes all the same: masked_relu, the kernels' !(y <= 0))
     ref.backward(gmap)
     _check_discriminates(ref.detach())
     assert_parity_t(out.detach(), ref.detach(), "training forward, non-finite features (NaN / inf pattern)")

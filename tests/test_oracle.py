@@ -189,3 +189,28 @@ def test_sort_order_restatement_matches_torch_cpu_sort():
         ref = torch.from_numpy(x).sort(0)[1].tolist()
         assert postproc.std_sort_order(x) == ref, len(x)
         assert postproc.level_sort_order(x) == ref, len(x)
+
+
+@pytest.mark.parametrize("n", [7, 25, 1031])
+def test_masked_relu_is_torch_relu_nan_included(n):
+    """``helpers.masked_relu`` (the ReLU of the non-finite training reference, with the GPU's activation
+    pattern) on the pinned torch CPU: with m = (pre > 0) it is ``F.relu`` bit for bit, value and gradient,
+    on NaN, +-inf, +-0, a denormal and ordinary values — a short tensor (torch's scalar loop) and
+    vector-length ones.  ``nn.ReLU``'s backward is ``threshold_backward``: the gradient PASSES at a NaN."""
+    from helpers import masked_relu
+    g = torch.Generator().manual_seed(n)
+    special = torch.tensor([float("nan"), float("inf"), float("-inf"), 0.0, -0.0, 1e-40, -1e-40])
+    pre = torch.randn(n, generator=g)
+    pre[torch.arange(0, n, 3)] = special.repeat(n)[:len(range(0, n, 3))]
+    grad = torch.randn(n, generator=g) + 3.0
+    a, b = pre.clone().requires_grad_(), pre.clone().requires_grad_()
+    ya, yb = masked_relu(a, (pre > 0).float()), F.relu(b)
+    ya.backward(grad)
+    yb.backward(grad)
+    for got, ref in ((ya.detach(), yb.detach()), (a.grad, b.grad)):
+        assert torch.equal(torch.isnan(got), torch.isnan(ref))
+        ok = ~torch.isnan(ref)
+        assert torch.equal(got[ok].view(torch.int32), ref[ok].view(torch.int32))
+    nan = torch.isnan(pre)
+    assert nan.any() and torch.equal(b.grad[nan], grad[nan])  # torch passes the gradient at a NaN
+    assert torch.equal(b.grad, torch.ops.aten.threshold_backward(grad, yb.detach(), 0))

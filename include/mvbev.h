@@ -846,6 +846,52 @@ int mvbev_loss_finalize_f32(const mvbev_loss_item* items, int n, int64_t B, cons
 int mvbev_gaussian_mse_backward_f32(const mvbev_loss_item* items, int n, int64_t B, const float* grad_out,
                                     float* const* grads, void* stream);
 
+/* ---- image head (persp_trans_detector.py:65-66 after the head's first 1x1 conv) ----
+ * Added after 12400 (mvbev_version() stays 12400): mvbev_img_head_forward_f32,
+ * mvbev_img_head_backward_blocks, mvbev_img_head_backward_f32, mvbev_img_head_grad_weight_f32.
+ *   out = conv2d(relu(F.interpolate(g, (Hu, Wu), mode="bilinear")), weight)    (1x1, no bias)
+ * for every view in one launch, fp32.  Per output pixel: the four align_corners=False taps of
+ * every channel (all four always multiplied, so 0 * inf and 0 * NaN give NaN as in the reference),
+ * ReLU that keeps NaN, then the Co dot products.  The upsampled tensor is never written; the
+ * backward recomputes it from g.  Range: Cm <= 256, Co <= 4, Hu >= h, Wu >= w, n <= 16 views, every
+ * tensor below 2^31 elements (else MVBEV_ERR_SHAPE; a size <= 0 is MVBEV_ERR_RANK, a negative
+ * stride MVBEV_ERR_STRIDE, a missing pointer MVBEV_ERR_NULL). */
+typedef struct mvbev_img_head_item {
+  const float* g;              /* [B][Cm][h][w], element strides g_strides (any, >= 0): NCHW planes
+                                * and torch channels_last both run without a copy */
+  int64_t g_strides[4];
+  float* out;                  /* forward: [B][Co][Hu][Wu], element strides out_strides */
+  int64_t out_strides[4];
+  const float* grad_out;       /* backward: d loss / d out, [B][Co][Hu][Wu], strides grad_out_strides;
+                                * NULL: this view took no part in the loss (no grad_g is written and it
+                                * adds nothing to grad_W) */
+  int64_t grad_out_strides[4];
+  float* grad_g;               /* backward: [B][Cm][h][w], strides grad_g_strides; NULL: not wanted */
+  int64_t grad_g_strides[4];
+} mvbev_img_head_item;
+
+/* weight: device [Co][Cm] contiguous.  One workgroup per (view, b, 8 x 32 output tile). */
+int mvbev_img_head_forward_f32(const mvbev_img_head_item* items, int n, int64_t B, int64_t Cm, int64_t h, int64_t w,
+                               int64_t Co, int64_t Hu, int64_t Wu, const float* weight, void* stream);
+
+/* Workgroups of mvbev_img_head_backward_f32 over these items (the views with a grad_out) = columns
+ * of its partials (0: invalid arguments or no such view). */
+int64_t mvbev_img_head_backward_blocks(const mvbev_img_head_item* items, int n, int64_t B, int64_t Cm, int64_t h,
+                                       int64_t w, int64_t Co, int64_t Hu, int64_t Wu);
+
+/* grad_g = U^T(mask * (W^T grad_out)) in gather form (every backbone pixel sums the output pixels
+ * whose taps reach it, in a fixed order; mask = !(pre <= 0), so the gradient passes at NaN as in
+ * threshold_backward), and, when partials is not NULL, the per-workgroup sums of
+ * grad_out[o] * relu(pre[c]) as partials[Co * Cm][blocks] (device fp32, npartials >= Co * Cm *
+ * mvbev_img_head_backward_blocks values, every one written).  No float atomics: bitwise repeatable. */
+int mvbev_img_head_backward_f32(const mvbev_img_head_item* items, int n, int64_t B, int64_t Cm, int64_t h, int64_t w,
+                                int64_t Co, int64_t Hu, int64_t Wu, const float* weight, float* partials,
+                                int64_t npartials, void* stream);
+
+/* grad_w[Co][Cm] = the row sums of partials[Co * Cm][nblocks], in a fixed order in fp64. */
+int mvbev_img_head_grad_weight_f32(const float* partials, int64_t nblocks, int64_t Cm, int64_t Co, float* grad_w,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

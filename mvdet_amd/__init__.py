@@ -11,6 +11,8 @@ Public surface (mirrors the reference's):
 * ``GaussianMSE`` / ``detection_loss`` / ``gaussian_kernels`` — drop-ins for
   ``multiview_detector.loss.gaussian_mse.GaussianMSE`` and the loss / precision-recall lines of
   ``trainer.py:43-56`` (``mvdet_amd.loss``).
+* ``upsample_relu_conv1x1`` — the image head after its first conv (bilinear upsample, ReLU, 1x1
+  conv) for all views in one launch, with a native backward (``mvdet_amd.img_head``).
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -21,6 +23,8 @@ from .pipeline import ProjectFuse  # noqa: F401
 from . import postprocess  # noqa: F401
 from . import loss  # noqa: F401
 from .loss import GaussianMSE, detection_loss, gaussian_kernels  # noqa: F401
+from . import img_head  # noqa: F401
+from .img_head import upsample_relu_conv1x1  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
-           "detection_loss", "gaussian_kernels"]
+           "detection_loss", "gaussian_kernels", "img_head", "upsample_relu_conv1x1"]

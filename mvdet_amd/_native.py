@@ -106,6 +106,11 @@ EXPORTS = (
     "mvbev_gaussian_mse_f32",
     "mvbev_loss_finalize_f32",
     "mvbev_gaussian_mse_backward_f32",
+    # the fused image head (added after 12400; the version stays 12400)
+    "mvbev_img_head_forward_f32",
+    "mvbev_img_head_backward_blocks",
+    "mvbev_img_head_backward_f32",
+    "mvbev_img_head_grad_weight_f32",
 )
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
 BEV_SRC_CHANNELS_LAST = 16  # MVBEV_BEV_SRC_CHANNELS_LAST (flag)
@@ -184,6 +189,14 @@ class LossKernel(ctypes.Structure):
     """``mvbev_loss_kernel`` (include/mvbev.h)."""
     _fields_ = [("w", ctypes.c_void_p), ("C", ctypes.c_int64), ("k", ctypes.c_int64),
                 ("slice_mask", ctypes.c_uint64), ("finite", ctypes.c_int32)]
+
+
+class ImgHeadItem(ctypes.Structure):
+    """``mvbev_img_head_item`` (include/mvbev.h)."""
+    _fields_ = [("g", ctypes.c_void_p), ("g_strides", ctypes.c_int64 * 4), ("out", ctypes.c_void_p),
+                ("out_strides", ctypes.c_int64 * 4), ("grad_out", ctypes.c_void_p),
+                ("grad_out_strides", ctypes.c_int64 * 4), ("grad_g", ctypes.c_void_p),
+                ("grad_g_strides", ctypes.c_int64 * 4)]
 
 
 class NativeError(RuntimeError):
@@ -419,6 +432,16 @@ def _declare(lib):
     lib.mvbev_loss_finalize_f32.argtypes = [items, ctypes.c_int, _i64, _p, _i64, ctypes.c_int, _p, _p, _p]
     lib.mvbev_gaussian_mse_backward_f32.restype = ctypes.c_int
     lib.mvbev_gaussian_mse_backward_f32.argtypes = [items, ctypes.c_int, _i64, _p, ctypes.POINTER(ctypes.c_void_p), _p]
+    views = ctypes.POINTER(ImgHeadItem)
+    dims = [_i64] * 7  # B, Cm, h, w, Co, Hu, Wu
+    lib.mvbev_img_head_forward_f32.restype = ctypes.c_int
+    lib.mvbev_img_head_forward_f32.argtypes = [views, ctypes.c_int] + dims + [_p, _p]
+    lib.mvbev_img_head_backward_blocks.restype = _i64
+    lib.mvbev_img_head_backward_blocks.argtypes = [views, ctypes.c_int] + dims
+    lib.mvbev_img_head_backward_f32.restype = ctypes.c_int
+    lib.mvbev_img_head_backward_f32.argtypes = [views, ctypes.c_int] + dims + [_p, _p, _i64, _p]
+    lib.mvbev_img_head_grad_weight_f32.restype = ctypes.c_int
+    lib.mvbev_img_head_grad_weight_f32.argtypes = [_p, _i64, _i64, _i64, _p, _p]
 
 
 def load(path: os.PathLike | str | None = None):

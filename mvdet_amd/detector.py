@@ -12,7 +12,9 @@ HIP kernels of ``libmvbev.so`` through ``ProjectFuse``:
 * the 3x upsample of ``:65`` is fused into the warp (the 265 MB/view upsampled map is
   never written) and all views warp in one launch, straight into the fused tensor;
 * the image head's first 1x1 conv runs before the upsample (64 instead of 512 channels
-  upsampled; it commutes with bilinear interpolation);
+  upsampled; it commutes with bilinear interpolation), and the rest of the head (upsample, ReLU,
+  second 1x1 conv) runs as one fused HIP launch over all views, forward and backward
+  (``img_head.upsample_relu_conv1x1``; ``native_img_head=False`` keeps the torch ops);
 * the coord channels are written once, not copied every forward;
 * conv1/conv2 are MFMA implicit GEMMs (default 3xbf16 split precision, fp32
   accumulation — same parity as exact fp32; ``precision="fp32"`` selects the
@@ -34,6 +36,7 @@ import torch.nn.functional as F
 
 from . import _native
 from . import autograd as native_autograd
+from . import img_head
 from .backbone import build_backbone
 from .geometry import coord_map as make_coord_map
 from .geometry import projection_matrices, upsample_shape
@@ -42,7 +45,8 @@ from .pipeline import ProjectFuse
 
 class PerspTransDetector(nn.Module):
     def __init__(self, dataset, arch: str = "resnet18", device=None, precision: str = "bf16x3",
-                 wino_conv1: bool = True, wino_conv2: bool = True, channels_last: bool = True):
+                 wino_conv1: bool = True, wino_conv2: bool = True, channels_last: bool = True,
+                 native_img_head: bool = True):
         super().__init__()
         self.num_cam = dataset.num_cam
         self.img_shape, self.reducedgrid_shape = list(dataset.img_shape), list(dataset.reducedgrid_shape)
@@ -66,6 +70,9 @@ class PerspTransDetector(nn.Module):
         # 0.39 ms), and the MIOpen backbone itself ran no slower (7 x 720 x 1280: 21.4 vs 22.8 ms,
         # profiles/r05ah_backbone_layout.json)
         self.channels_last = bool(channels_last)
+        # on: the image head after its first conv as one fused launch over the views (img_head.py), inference and
+        # training; off: the torch ops per view inside the camera loop (F.interpolate, F.relu, the second conv)
+        self.native_img_head = bool(native_img_head)
         if self.channels_last:
             self.base_pt1.to(memory_format=torch.channels_last)
             self.base_pt2.to(memory_format=torch.channels_last)
@@ -86,7 +93,8 @@ class PerspTransDetector(nn.Module):
             raise RuntimeError("PerspTransDetector.forward needs a ROCm GPU (the hot path has no CPU fallback)")
         training = self._needs_autograd()
         ws = None if training else self.engine.workspace(B, dev)
-        imgs_result, low = [], []
+        imgs_result, low, head_low = [], [], []
+        split_head, native_head = self._img_head_splits(), None
         for cam in range(self.num_cam):
             x = imgs[:, cam].to(dev)
             feat = self.base_pt1(x.contiguous(memory_format=torch.channels_last) if self.channels_last else x)
@@ -94,7 +102,17 @@ class PerspTransDetector(nn.Module):
             # the image head runs its first 1x1 conv before upsampling (it commutes with the
             # bilinear upsample: per-pixel affine, weights summing to 1) on 64 instead of 512
             # channels
-            imgs_result.append(self._img_head_lowres(feat))
+            if split_head:
+                g = self.img_classifier[0](feat)
+                if native_head is None:
+                    native_head = self._img_head_native(g)
+                if native_head:
+                    head_low.append(g)  # all views go through one fused launch after the loop
+                else:
+                    imgs_result.append(self.img_classifier[2](
+                        F.relu(F.interpolate(g, self.upsample_shape, mode="bilinear"))))
+            else:
+                imgs_result.append(self.img_classifier(F.interpolate(feat, self.upsample_shape, mode="bilinear")))
             # the 3x upsample (:65) happens inside the fused warp below (and, training, its
             # adjoint inside the warp adjoint)
             # (a channels-last backbone's maps stay channels-last: the fused warp's line-per-pixel kernel)
@@ -103,6 +121,9 @@ class PerspTransDetector(nn.Module):
             if visualize:
                 up = F.interpolate(feat, self.upsample_shape, mode="bilinear")
                 self._show(torch.norm(up[0].detach(), dim=0))
+        if head_low:
+            imgs_result = img_head.upsample_relu_conv1x1(head_low, self.img_classifier[2].weight,
+                                                         tuple(self.upsample_shape))
         if training:  # a4-a9 forward and backward on the HIP kernels (autograd.py)
             map_result = native_autograd.project_fuse_backbone(self.engine, low, self.map_classifier)
         else:
@@ -112,15 +133,22 @@ class PerspTransDetector(nn.Module):
             self._show(torch.norm(map_result[0].detach(), dim=0))
         return map_result, imgs_result
 
-    def _img_head_lowres(self, feat: torch.Tensor) -> torch.Tensor:
-        """``img_classifier(F.interpolate(feat, upsample_shape))`` (:65-66) evaluated as
-        conv_b(relu(upsample(conv_a(feat)))): identical in exact arithmetic."""
+    def _img_head_splits(self) -> bool:
+        """Whether ``img_classifier`` is Conv2d(1x1) -> ReLU -> module, so that its first conv can run
+        before the upsample: ``img_classifier(F.interpolate(feat, upsample_shape))`` (:65-66) evaluated
+        as head[2](relu(upsample(head[0](feat)))), identical in exact arithmetic."""
         head = self.img_classifier
-        if (len(head) == 3 and isinstance(head[0], nn.Conv2d) and head[0].kernel_size == (1, 1)
-                and isinstance(head[1], nn.ReLU)):
-            g = head[0](feat)
-            return head[2](F.relu(F.interpolate(g, self.upsample_shape, mode="bilinear")))
-        return head(F.interpolate(feat, self.upsample_shape, mode="bilinear"))
+        return (len(head) == 3 and isinstance(head[0], nn.Conv2d) and head[0].kernel_size == (1, 1)
+                and isinstance(head[1], nn.ReLU))
+
+    def _img_head_native(self, g: torch.Tensor) -> bool:
+        """Whether relu(upsample(g)) -> head[2] runs as the fused HIP op: the flag is on, the second conv is a
+        plain bias-free 1x1 conv, everything is fp32 and the shape is inside the kernels' range."""
+        last = self.img_classifier[2]
+        return (self.native_img_head and isinstance(last, nn.Conv2d) and last.kernel_size == (1, 1)
+                and last.stride == (1, 1) and last.padding == (0, 0) and last.groups == 1 and last.bias is None
+                and last.weight.dtype == torch.float32 and g.dtype == torch.float32 and g.is_cuda
+                and img_head.supported(self.num_cam, g.shape, last.out_channels, tuple(self.upsample_shape)))
 
     @staticmethod
     def _show(img):

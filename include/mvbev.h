@@ -892,6 +892,56 @@ int mvbev_img_head_backward_f32(const mvbev_img_head_item* items, int n, int64_t
 int mvbev_img_head_grad_weight_f32(const float* partials, int64_t nblocks, int64_t Cm, int64_t Co, float* grad_w,
                                    void* stream);
 
+/* ---- warp-sum head (no_joint_conv_variant.py:64-81 after map_classifier[0] moved in front) ----
+ * Added after 12400 (mvbev_version() stays 12400): mvbev_warp_sum_head_forward_f32,
+ * mvbev_warp_sum_head_backward_blocks, mvbev_warp_sum_head_backward_f32,
+ * mvbev_warp_sum_head_grad_params_f32.
+ * The "no joint spatial reasoning" ablation upsamples every view's 512-channel map (:64), warps it
+ * (:68), concatenates the views with the two coord channels (:76) and applies Conv2d(512 N + 2, 512, 1),
+ * ReLU, Conv2d(512, 1, 1, bias=False) (:51-53, :80).  The 1x1 conv commutes with the upsample and the
+ * warp (both linear per channel), so with z_v = W_v feat_v at backbone resolution (a GEMM, the caller's):
+ *   hidden[b, :, p] = relu(bias + w_coord . coord(p) + sum_v warp_v(upsample(z_v))[b, :, p])
+ *   map[b, 0, p]    = w2 . hidden[b, :, p]
+ * in one launch: no upsampled map, no concatenated slab and, with hidden == NULL, nothing of
+ * [B][Cm][Ho][Wo] is written.
+ *
+ * views[i]: src = z_i [B][Cm][h][w] fp32 with channel stride 1 (channels-last lines; batch, row and
+ * column strides free, >= 0), m = the kornia matrix for the upsampled size H x W (as
+ * mvbev_warp_views_upsampled), dst unused.  bias [Cm], w_coord [Cm][2] (x, y), w2 [Cm], map
+ * [B][1][Ho][Wo] contiguous, hidden [B][Cm][Ho][Wo] contiguous planes (the post-ReLU values) or NULL.
+ * boxes: NULL, or the int32 [nviews][tiles][4] of mvbev_warp_upsampled_wino_boxes for the same
+ * matrices and sizes with r3_rows = 4 ceil(Ho / 12) (geometry only: a view whose box says that it
+ * reaches no pixel of a tile is not evaluated there).  The sample window is the folded 3x3 backbone
+ * window of mvbev_warp_views_upsampled, the one mvbev_warp_upsampled_adjoint_plan transposes; the
+ * coord values are those of mvbev_fill_coord_map_f32.  A pixel whose sample coordinates are not
+ * finite for some view is NaN; a pixel outside a view's source gets exactly 0 from that view (its
+ * data is not read).  NaN / Inf in z or the parameters are outside the contract: the commuted order
+ * cannot reproduce where the reference's 0 * NaN lands.
+ * Range: 1 <= nviews <= 16, 1 <= Cm <= 512 (any, not only multiples of 4), H >= h, W >= w (else
+ * MVBEV_ERR_SHAPE; a size <= 0 is MVBEV_ERR_RANK, a channel stride != 1 or a negative stride
+ * MVBEV_ERR_STRIDE, a missing pointer MVBEV_ERR_NULL). */
+int mvbev_warp_sum_head_forward_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t Cm, int64_t h,
+                                    int64_t w, int64_t H, int64_t W, int64_t Ho, int64_t Wo, const float* bias,
+                                    const float* w_coord, const float* w2, float* map, float* hidden,
+                                    const int32_t* boxes, void* stream);
+
+/* Columns of mvbev_warp_sum_head_backward_f32's partials: B * ceil(Ho * Wo / 4096) (0: invalid sizes). */
+int64_t mvbev_warp_sum_head_backward_blocks(int64_t B, int64_t Cm, int64_t Ho, int64_t Wo);
+
+/* dhidden[b, c, p] = hidden[b, c, p] <= 0 ? 0 : dmap[b, p] * w2[c] (mvbev_relu_backward_f32's rule: the
+ * gradient passes where hidden is NaN), [B][Cm][Ho][Wo] planes that may alias hidden (NULL: not
+ * wanted), and, when partials is not NULL, the per-workgroup sums partials[4][Cm][blocks] (blocks =
+ * mvbev_warp_sum_head_backward_blocks) of dmap * hidden (grad_w2), dhidden (grad_bias), dhidden * x and
+ * dhidden * y (grad_w_coord), every one written.  The gradient to z_v is mvbev_warp_views_adjoint of
+ * dhidden with the plan of mvbev_warp_upsampled_adjoint_plan.  No float atomics: bitwise repeatable. */
+int mvbev_warp_sum_head_backward_f32(const float* dmap, const float* hidden, const float* w2, int64_t B, int64_t Cm,
+                                     int64_t Ho, int64_t Wo, float* dhidden, float* partials, void* stream);
+
+/* grad_w2 [Cm], grad_bias [Cm], grad_w_coord [Cm][2] (each may be NULL: not wanted) = the row sums of
+ * partials[4 * Cm][nblocks], in a fixed order in fp64. */
+int mvbev_warp_sum_head_grad_params_f32(const float* partials, int64_t nblocks, int64_t Cm, float* grad_w2,
+                                        float* grad_bias, float* grad_w_coord, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

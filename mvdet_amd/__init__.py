@@ -13,6 +13,9 @@ Public surface (mirrors the reference's):
   ``trainer.py:43-56`` (``mvdet_amd.loss``).
 * ``upsample_relu_conv1x1`` — the image head after its first conv (bilinear upsample, ReLU, 1x1
   conv) for all views in one launch, with a native backward (``mvdet_amd.img_head``).
+* ``NoJointConvVariant`` — drop-in for ``multiview_detector.models.no_joint_conv_variant.NoJointConvVariant``
+  (``mvdet_amd.variants``); ``ProjectSumHead`` — its ground-plane head after the first 1x1 conv (upsample,
+  warp, sum over views, ReLU, second conv) as one launch with a native backward (``mvdet_amd.sum_head``).
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -25,6 +28,10 @@ from . import loss  # noqa: F401
 from .loss import GaussianMSE, detection_loss, gaussian_kernels  # noqa: F401
 from . import img_head  # noqa: F401
 from .img_head import upsample_relu_conv1x1  # noqa: F401
+from . import sum_head  # noqa: F401
+from .sum_head import ProjectSumHead  # noqa: F401
+from .variants import NoJointConvVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
-           "detection_loss", "gaussian_kernels", "img_head", "upsample_relu_conv1x1"]
+           "detection_loss", "gaussian_kernels", "img_head", "upsample_relu_conv1x1",
+           "sum_head", "ProjectSumHead", "NoJointConvVariant"]

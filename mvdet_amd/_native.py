@@ -111,6 +111,11 @@ EXPORTS = (
     "mvbev_img_head_backward_blocks",
     "mvbev_img_head_backward_f32",
     "mvbev_img_head_grad_weight_f32",
+    # the warp-sum head of NoJointConvVariant (added after 12400; the version stays 12400)
+    "mvbev_warp_sum_head_forward_f32",
+    "mvbev_warp_sum_head_backward_blocks",
+    "mvbev_warp_sum_head_backward_f32",
+    "mvbev_warp_sum_head_grad_params_f32",
 )
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
 BEV_SRC_CHANNELS_LAST = 16  # MVBEV_BEV_SRC_CHANNELS_LAST (flag)
@@ -442,6 +447,15 @@ def _declare(lib):
     lib.mvbev_img_head_backward_f32.argtypes = [views, ctypes.c_int] + dims + [_p, _p, _i64, _p]
     lib.mvbev_img_head_grad_weight_f32.restype = ctypes.c_int
     lib.mvbev_img_head_grad_weight_f32.argtypes = [_p, _i64, _i64, _i64, _p, _p]
+    lib.mvbev_warp_sum_head_forward_f32.restype = ctypes.c_int
+    lib.mvbev_warp_sum_head_forward_f32.argtypes = ([ctypes.POINTER(WarpView), ctypes.c_int] + [_i64] * 8 +
+                                                    [_p] * 7)  # bias, w_coord, w2, map, hidden, boxes, stream
+    lib.mvbev_warp_sum_head_backward_blocks.restype = _i64
+    lib.mvbev_warp_sum_head_backward_blocks.argtypes = [_i64] * 4
+    lib.mvbev_warp_sum_head_backward_f32.restype = ctypes.c_int
+    lib.mvbev_warp_sum_head_backward_f32.argtypes = [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]
+    lib.mvbev_warp_sum_head_grad_params_f32.restype = ctypes.c_int
+    lib.mvbev_warp_sum_head_grad_params_f32.argtypes = [_p, _i64, _i64, _p, _p, _p, _p]
 
 
 def load(path: os.PathLike | str | None = None):

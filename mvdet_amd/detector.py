@@ -43,11 +43,13 @@ from .geometry import projection_matrices, upsample_shape
 from .pipeline import ProjectFuse
 
 
-class PerspTransDetector(nn.Module):
-    def __init__(self, dataset, arch: str = "resnet18", device=None, precision: str = "bf16x3",
-                 wino_conv1: bool = True, wino_conv2: bool = True, channels_last: bool = True,
-                 native_img_head: bool = True):
-        super().__init__()
+class _ViewsDetector(nn.Module):
+    """What the reference's detector variants share (``persp_trans_detector.py`` and
+    ``no_joint_conv_variant.py`` repeat it verbatim): the dataset attributes, the backbone halves, the image
+    head, the per-view part of ``forward`` and the reference's helper methods.  A subclass adds its
+    ``map_classifier`` between ``_init_views`` and ``_place``, which keeps the reference's ``state_dict`` order."""
+
+    def _init_views(self, dataset, arch: str, device, channels_last: bool, native_img_head: bool) -> int:
         self.num_cam = dataset.num_cam
         self.img_shape, self.reducedgrid_shape = list(dataset.img_shape), list(dataset.reducedgrid_shape)
         self.coord_map = make_coord_map(*self.reducedgrid_shape)          # :21 (not a buffer)
@@ -61,38 +63,29 @@ class PerspTransDetector(nn.Module):
         self.base_pt1, self.base_pt2, out_channel = build_backbone(arch)
         self.img_classifier = nn.Sequential(nn.Conv2d(out_channel, 64, 1), nn.ReLU(),
                                             nn.Conv2d(64, 2, 1, bias=False))
-        self.map_classifier = nn.Sequential(nn.Conv2d(out_channel * self.num_cam + 2, 512, 3, padding=1), nn.ReLU(),
-                                            nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),
-                                            nn.Conv2d(512, 1, 3, padding=4, dilation=4, bias=False))
+        self.channels_last = bool(channels_last)
+        # on: the image head after its first conv as one fused launch over the views (img_head.py), inference and
+        # training; off: the torch ops per view inside the camera loop (F.interpolate, F.relu, the second conv)
+        self.native_img_head = bool(native_img_head)
+        return out_channel
+
+    def _place(self) -> None:
         self.to(self._device)
         # the backbone in torch's channels_last memory format (the same weights and state_dict): its maps then
         # reach the fused upsample warp's line-per-pixel kernel without a transposing copy (cfg2: 0.29-0.32 vs
         # 0.39 ms), and the MIOpen backbone itself ran no slower (7 x 720 x 1280: 21.4 vs 22.8 ms,
         # profiles/r05ah_backbone_layout.json)
-        self.channels_last = bool(channels_last)
-        # on: the image head after its first conv as one fused launch over the views (img_head.py), inference and
-        # training; off: the torch ops per view inside the camera loop (F.interpolate, F.relu, the second conv)
-        self.native_img_head = bool(native_img_head)
         if self.channels_last:
             self.base_pt1.to(memory_format=torch.channels_last)
             self.base_pt2.to(memory_format=torch.channels_last)
-        # conv1 and conv2 as row-Winograd F(3,3) (ProjectFuse.conv1_wino, conv2_partials), inference and
-        # training (forward, data and weight gradients: autograd.py)
-        self.engine = ProjectFuse(self.proj_mats, tuple(self.upsample_shape), tuple(self.reducedgrid_shape),
-                                  out_channel, precision=precision, wino_conv1=wino_conv1, wino_conv2=wino_conv2)
 
-    # -- hot path --------------------------------------------------------------------------
     def _needs_autograd(self) -> bool:
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
-    def forward(self, imgs: torch.Tensor, visualize: bool = False):
-        B, N, C, H, W = imgs.shape
-        assert N == self.num_cam
+    def _views_forward(self, imgs: torch.Tensor, visualize: bool = False):
+        """The camera loop up to the warp: every view's backbone map (channels-last when the backbone is) and
+        the image head's results (``:62-66``)."""
         dev = self._device
-        if dev.type != "cuda":
-            raise RuntimeError("PerspTransDetector.forward needs a ROCm GPU (the hot path has no CPU fallback)")
-        training = self._needs_autograd()
-        ws = None if training else self.engine.workspace(B, dev)
         imgs_result, low, head_low = [], [], []
         split_head, native_head = self._img_head_splits(), None
         for cam in range(self.num_cam):
@@ -124,14 +117,7 @@ class PerspTransDetector(nn.Module):
         if head_low:
             imgs_result = img_head.upsample_relu_conv1x1(head_low, self.img_classifier[2].weight,
                                                          tuple(self.upsample_shape))
-        if training:  # a4-a9 forward and backward on the HIP kernels (autograd.py)
-            map_result = native_autograd.project_fuse_backbone(self.engine, low, self.map_classifier)
-        else:
-            self.engine.warp_views_upsampled(ws, list(range(self.num_cam)), low)  # a4 + a5 + a6
-            map_result = self.engine.fuse(ws, self.map_classifier)
-        if visualize:
-            self._show(torch.norm(map_result[0].detach(), dim=0))
-        return map_result, imgs_result
+        return low, imgs_result
 
     def _img_head_splits(self) -> bool:
         """Whether ``img_classifier`` is Conv2d(1x1) -> ReLU -> module, so that its first conv can run
@@ -170,3 +156,38 @@ class PerspTransDetector(nn.Module):
             rr = torch.sqrt(ret[:, 0] ** 2 + ret[:, 1] ** 2).view([1, 1, H, W])
             ret = torch.cat([ret, rr], dim=1)
         return ret
+
+
+class PerspTransDetector(_ViewsDetector):
+    def __init__(self, dataset, arch: str = "resnet18", device=None, precision: str = "bf16x3",
+                 wino_conv1: bool = True, wino_conv2: bool = True, channels_last: bool = True,
+                 native_img_head: bool = True):
+        super().__init__()
+        out_channel = self._init_views(dataset, arch, device, channels_last, native_img_head)
+        self.map_classifier = nn.Sequential(nn.Conv2d(out_channel * self.num_cam + 2, 512, 3, padding=1), nn.ReLU(),
+                                            nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),
+                                            nn.Conv2d(512, 1, 3, padding=4, dilation=4, bias=False))
+        self._place()
+        # conv1 and conv2 as row-Winograd F(3,3) (ProjectFuse.conv1_wino, conv2_partials), inference and
+        # training (forward, data and weight gradients: autograd.py)
+        self.engine = ProjectFuse(self.proj_mats, tuple(self.upsample_shape), tuple(self.reducedgrid_shape),
+                                  out_channel, precision=precision, wino_conv1=wino_conv1, wino_conv2=wino_conv2)
+
+    # -- hot path --------------------------------------------------------------------------
+    def forward(self, imgs: torch.Tensor, visualize: bool = False):
+        B, N, C, H, W = imgs.shape
+        assert N == self.num_cam
+        dev = self._device
+        if dev.type != "cuda":
+            raise RuntimeError("PerspTransDetector.forward needs a ROCm GPU (the hot path has no CPU fallback)")
+        training = self._needs_autograd()
+        ws = None if training else self.engine.workspace(B, dev)
+        low, imgs_result = self._views_forward(imgs, visualize)
+        if training:  # a4-a9 forward and backward on the HIP kernels (autograd.py)
+            map_result = native_autograd.project_fuse_backbone(self.engine, low, self.map_classifier)
+        else:
+            self.engine.warp_views_upsampled(ws, list(range(self.num_cam)), low)  # a4 + a5 + a6
+            map_result = self.engine.fuse(ws, self.map_classifier)
+        if visualize:
+            self._show(torch.norm(map_result[0].detach(), dim=0))
+        return map_result, imgs_result

@@ -86,3 +86,15 @@ def load_reference_detector():
     matplotlib.use("Agg")
     from multiview_detector.models.persp_trans_detector import PerspTransDetector
     return PerspTransDetector
+
+
+def load_reference_no_joint_conv_variant():
+    """The reference's ``NoJointConvVariant`` (``tools/gen_golden_variant.py``); it calls the top-level
+    ``kornia.warp_perspective`` alias, stubbed above with the same restatement."""
+    _install_stubs()
+    if REF_ROOT not in sys.path:
+        sys.path.insert(0, REF_ROOT)
+    import matplotlib
+    matplotlib.use("Agg")
+    from multiview_detector.models.no_joint_conv_variant import NoJointConvVariant
+    return NoJointConvVariant

@@ -942,6 +942,58 @@ int mvbev_warp_sum_head_backward_f32(const float* dmap, const float* hidden, con
 int mvbev_warp_sum_head_grad_params_f32(const float* partials, int64_t nblocks, int64_t Cm, float* grad_w2,
                                         float* grad_bias, float* grad_w_coord, void* stream);
 
+/* ---- thin fused conv1 (res_proj_variant.py:53, :70-82: the "late fusion" head's first conv) ----
+ * Added after 12400 (mvbev_version() stays 12400): mvbev_thin_conv1_forward_f32,
+ * mvbev_thin_conv1_backward_blocks, mvbev_thin_conv1_backward_f32, mvbev_thin_conv1_grad_weight_f32.
+ * The late-fusion ablation warps ONE plane per view (the foot channel of the image result, :72), concatenates
+ * the N warped planes with the two coord channels (:81) and applies Conv2d(N + 2, Cout, 3, padding=1), ReLU
+ * (:53).  In one launch:
+ *   x[b][c][r][u], c < N      = the kornia warp of view c's plane (mvbev_warp_perspective_f32's coordinates,
+ *                               bilinear blend and zero padding; non-finite coordinates give NaN)
+ *   x[b][N], x[b][N + 1]      = the coord values of mvbev_fill_coord_map_f32
+ *   y1[b][co][r][u]           = relu(b1[co] + sum_{c < N + 2} sum_{kh, kw} w1[co][c][kh][kw] x[b][c][r + kh - 1][u + kw - 1])
+ * with x zero outside the grid (coord channels included: nn.Conv2d's padding), products and sums in fp32 in a
+ * fixed order, a ReLU that keeps NaN, and every tap multiplied: a NaN sample reaches exactly its 3 x 3
+ * neighbourhood in every output channel.  A view whose samples over a tile and its halo all fall outside its
+ * source adds exact zeros and is not evaluated there (geometry only).
+ *
+ * views[i]: src = the plane [B][1][H][W] fp32 at element strides src_strides (batch and row strides >= 0, column
+ * stride 1, the channel stride is not read: a channel slice of a wider tensor runs without a copy), m = the
+ * kornia matrix; dst unused.  w1 [Cout][N + 2][3][3] fp32 contiguous (the module's own tensor, no packing),
+ * b1 [Cout] or NULL.  y1 contiguous in y1_layout: MVBEV_LAYOUT_F32 ([B][Cout][Ho][Wo]) or
+ * MVBEV_LAYOUT_SPLIT_BF16 ([B][Cout / 8][Ho][Wo] pieces of bf16 hi[8], lo[8], 16-B aligned: the input of
+ * mvbev_wino_rows_split_bf16_dil and the ring conv).  xw (NULL in inference): the N warped planes,
+ * [B][N][Ho][Wo] fp32 contiguous, which the backward reads.  NaN / Inf in the planes or the weights are outside
+ * the contract (a view skipped over a tile does not multiply them).
+ * Range: 1 <= nviews <= 16, Cout % 8 == 0, every tensor below 2^31 elements (else MVBEV_ERR_SHAPE, as an
+ * unknown layout; a size <= 0 is MVBEV_ERR_RANK, a column stride != 1 or a negative stride MVBEV_ERR_STRIDE, a
+ * missing pointer MVBEV_ERR_NULL, a misaligned split y1 MVBEV_ERR_ALIGN). */
+int mvbev_thin_conv1_forward_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t H, int64_t W, int64_t Ho,
+                                 int64_t Wo, const float* w1, const float* b1, int64_t Cout, void* y1, int y1_layout,
+                                 float* xw, void* stream);
+
+/* Workgroups of mvbev_thin_conv1_backward_f32's weight-gradient pass = the leading extent of its partials:
+ * B * ceil(Ho / 8) * ceil(Wo / 32) (0: invalid sizes). */
+int64_t mvbev_thin_conv1_backward_blocks(int64_t B, int64_t Ho, int64_t Wo);
+
+/* dpre [B][Cout][Ho][Wo] fp32 contiguous: the gradient of the pre-activation (the caller has applied the ReLU's
+ * mask).  dxw (NULL: not wanted; needs w1) [B][N][Ho][Wo] contiguous:
+ *   dxw[b][v][p] = sum_co sum_t w1[co][v][t] dpre[b][co][p - s_t]                              (v < N)
+ * partials (NULL: not wanted; needs xw) [blocks][Cout][N][9], npartials >= blocks * Cout * N * 9 values, every
+ * one written: the per-workgroup sums of
+ *   dw1[co][v][t] = sum_{b, p} dpre[b][co][p] xw[b][v][p + s_t]                                 (v < N)
+ * The bias gradient and the coord channels' weight gradient are mvbev_conv3x3_bias_coord_grad_f32's (coord_ch =
+ * N); the gradient to the planes is mvbev_warp_views_adjoint of dxw with mvbev_warp_adjoint_plan's plans (C = 1).
+ * Fixed summation order, no float atomics: bitwise repeatable.  Errors as the forward. */
+int mvbev_thin_conv1_backward_f32(const float* dpre, const float* w1, const float* xw, int nviews, int64_t B,
+                                  int64_t Cout, int64_t Ho, int64_t Wo, float* dxw, float* partials, int64_t npartials,
+                                  void* stream);
+
+/* dw[co][v][t] for v < N of a [Cout][N + 2][3][3] weight gradient (the two coord channels are not written) = the
+ * sums over the nblocks leading slices of partials, in order, in fp64. */
+int mvbev_thin_conv1_grad_weight_f32(const float* partials, int64_t nblocks, int nviews, int64_t Cout, float* dw,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,10 @@ Public surface (mirrors the reference's):
 * ``NoJointConvVariant`` — drop-in for ``multiview_detector.models.no_joint_conv_variant.NoJointConvVariant``
   (``mvdet_amd.variants``); ``ProjectSumHead`` — its ground-plane head after the first 1x1 conv (upsample,
   warp, sum over views, ReLU, second conv) as one launch with a native backward (``mvdet_amd.sum_head``).
+* ``ResProjVariant`` — drop-in for ``multiview_detector.models.res_proj_variant.ResProjVariant``
+  (``mvdet_amd.variants``); ``ProjectThinFuse`` — its ground-plane head: warp of the views' foot planes, coord
+  channels, the thin first conv, bias and ReLU as one launch, then the engine's conv2 / conv3, with a native
+  backward (``mvdet_amd.thin_fuse``).
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -30,8 +34,10 @@ from . import img_head  # noqa: F401
 from .img_head import upsample_relu_conv1x1  # noqa: F401
 from . import sum_head  # noqa: F401
 from .sum_head import ProjectSumHead  # noqa: F401
-from .variants import NoJointConvVariant  # noqa: F401
+from . import thin_fuse  # noqa: F401
+from .thin_fuse import ProjectThinFuse  # noqa: F401
+from .variants import NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
            "detection_loss", "gaussian_kernels", "img_head", "upsample_relu_conv1x1",
-           "sum_head", "ProjectSumHead", "NoJointConvVariant"]
+           "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant"]

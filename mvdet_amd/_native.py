@@ -116,6 +116,11 @@ EXPORTS = (
     "mvbev_warp_sum_head_backward_blocks",
     "mvbev_warp_sum_head_backward_f32",
     "mvbev_warp_sum_head_grad_params_f32",
+    # the thin fused conv1 of ResProjVariant (added after 12400; the version stays 12400)
+    "mvbev_thin_conv1_forward_f32",
+    "mvbev_thin_conv1_backward_blocks",
+    "mvbev_thin_conv1_backward_f32",
+    "mvbev_thin_conv1_grad_weight_f32",
 )
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
 BEV_SRC_CHANNELS_LAST = 16  # MVBEV_BEV_SRC_CHANNELS_LAST (flag)
@@ -456,6 +461,15 @@ def _declare(lib):
     lib.mvbev_warp_sum_head_backward_f32.argtypes = [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]
     lib.mvbev_warp_sum_head_grad_params_f32.restype = ctypes.c_int
     lib.mvbev_warp_sum_head_grad_params_f32.argtypes = [_p, _i64, _i64, _p, _p, _p, _p]
+    lib.mvbev_thin_conv1_forward_f32.restype = ctypes.c_int
+    lib.mvbev_thin_conv1_forward_f32.argtypes = ([ctypes.POINTER(WarpView), ctypes.c_int] + [_i64] * 5 +
+                                                 [_p, _p, _i64, _p, ctypes.c_int, _p, _p])  # w1, b1, Cout, y1, layout, xw
+    lib.mvbev_thin_conv1_backward_blocks.restype = _i64
+    lib.mvbev_thin_conv1_backward_blocks.argtypes = [_i64] * 3
+    lib.mvbev_thin_conv1_backward_f32.restype = ctypes.c_int
+    lib.mvbev_thin_conv1_backward_f32.argtypes = [_p, _p, _p, ctypes.c_int, _i64, _i64, _i64, _i64, _p, _p, _i64, _p]
+    lib.mvbev_thin_conv1_grad_weight_f32.restype = ctypes.c_int
+    lib.mvbev_thin_conv1_grad_weight_f32.argtypes = [_p, _i64, ctypes.c_int, _i64, _p, _p]
 
 
 def load(path: os.PathLike | str | None = None):

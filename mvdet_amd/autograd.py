@@ -278,6 +278,52 @@ def _wgrad_ws(st, desc, cout, device) -> torch.Tensor:
     return buf
 
 
+def backward_to_dy1(engine: ProjectFuse, st, ws: Workspace, w2, b2, w3, dmap, split_dy1: bool = True):
+    """The backward of conv3, conv2 and the two ReLUs from a training workspace (``ws.y1``, ``ws.y2``, conv2's T
+    where it ran row-Winograd): ``(dy1, dy1s, dw2, db2, dw3)`` with ``dy1`` the gradient of conv1's
+    pre-activation, fp32 ``[B, mid, H, W]`` already masked by conv1's ReLU, and ``dy1s`` the same in the split
+    layout (None with an fp32 y1, or without ``split_dy1``).  Shared by ``ProjectFuseFunction`` and
+    ``thin_fuse.ThinFuseFunction``, which differ only in conv1."""
+    H, W = engine.grid_hw
+    B = ws.y1.shape[0]
+    dev = ws.y1.device
+    y1_split = ws.y1.dtype == torch.bfloat16
+    dmap = dmap.contiguous().float()
+    mid = engine.mid
+    # conv3: dy2 = dgrad * relu'(y2); dw3
+    _mark("bwd_conv3")
+    # with split y1 the data gradients run on the ring kernel: dy2 also in the split layout
+    dy2s = torch.empty(ops.split_shape(B, mid, H, W), dtype=torch.bfloat16, device=dev) if y1_split else None
+    dy2, dw3 = ops.conv3x3_cout1_backward(ws.y2, w3, dmap, 4, relu_mask=True, dx_split=dy2s)
+    # conv2: db2, dw2, dy1 = dgrad * relu'(y1)
+    _mark("bwd_conv2_wgrad")
+    db2 = torch.empty(mid, dtype=torch.float32, device=dev) if b2 is not None else None
+    if db2 is not None:
+        ops.conv3x3_bias_coord_grad(dy2, 2, db=db2)
+    d_y1 = ops.conv_desc(B, mid, H, W, group=mid, group_stride=0, batch_stride=mid * H * W)
+    if ws.t2_valid and _wgrad_wino_fits(mid, mid, H, W, B, 2):  # from conv2's own T (ADVICE r05: the native limits)
+        dw2 = ops.conv3x3_wgrad_wino(ws.wino_t2, d_y1, ops.wino_dy_rows(dy2, dilation=2), mid, dilation=2,
+                                     workspace=_wgrad_wino_ws(st, d_y1, mid, 2, dev))
+    else:  # (the direct form reads the fp32 dy2: at its size the row split costs what it saves)
+        dw2 = ops.conv3x3_wgrad(ws.y1, d_y1, dy2, 2, mid, workspace=_wgrad_ws(st, d_y1, mid, dev))
+    _mark("bwd_conv2_dgrad")
+    if dy2s is not None and engine.wino_conv2_active(ws):
+        dy1 = _dgrad2_wino(engine, st, dy2s, w2)
+    else:
+        dy1 = ops.conv3x3_dgrad(dy2 if dy2s is None else dy2s, st.dgrad2, w2, 2)
+    if dy1.shape[1] != mid:
+        dy1 = dy1[:, :mid].contiguous()
+    del dy2, dy2s
+    dy1s = None
+    if y1_split:  # the masked dy1 also in the split layout: conv1's dgrad on the ring kernel
+        if split_dy1:
+            dy1s = torch.empty(ops.split_shape(B, mid, H, W), dtype=torch.bfloat16, device=dev)
+        ops.relu_backward_split_(dy1, ws.y1, dy1s)
+    else:
+        ops.relu_backward_(dy1, ws.y1)
+    return dy1, dy1s, dw2, db2, dw3
+
+
 class ProjectFuseFunction(torch.autograd.Function):
     """``map = fuse(concat(warp(feats[v]) for v) + coord)``; inputs after the engine and the
     ``backbone`` flag: the N view features, then conv1.w, conv1.b, conv2.w, conv2.b, conv3.w.
@@ -331,39 +377,8 @@ class ProjectFuseFunction(torch.autograd.Function):
         H, W = engine.grid_hw
         B = ws.y1.shape[0]
         dev = ws.y1.device
-        y1_split = ws.y1.dtype == torch.bfloat16
-        dmap = dmap.contiguous().float()
         mid = engine.mid
-        # conv3: dy2 = dgrad * relu'(y2); dw3
-        _mark("bwd_conv3")
-        # with split y1 the data gradients run on the ring kernel: dy2 also in the split layout
-        dy2s = torch.empty(ops.split_shape(B, mid, H, W), dtype=torch.bfloat16, device=dev) if y1_split else None
-        dy2, dw3 = ops.conv3x3_cout1_backward(ws.y2, w3, dmap, 4, relu_mask=True, dx_split=dy2s)
-        # conv2: db2, dw2, dy1 = dgrad * relu'(y1)
-        _mark("bwd_conv2_wgrad")
-        db2 = torch.empty(mid, dtype=torch.float32, device=dev) if b2 is not None else None
-        if db2 is not None:
-            ops.conv3x3_bias_coord_grad(dy2, 2, db=db2)
-        d_y1 = ops.conv_desc(B, mid, H, W, group=mid, group_stride=0, batch_stride=mid * H * W)
-        if ws.t2_valid and _wgrad_wino_fits(mid, mid, H, W, B, 2):  # from conv2's own T (the native limits)
-            dw2 = ops.conv3x3_wgrad_wino(ws.wino_t2, d_y1, ops.wino_dy_rows(dy2, dilation=2), mid, dilation=2,
-                                         workspace=_wgrad_wino_ws(st, d_y1, mid, 2, dev))
-        else:  # (the direct form reads the fp32 dy2: at its size the row split costs what it saves)
-            dw2 = ops.conv3x3_wgrad(ws.y1, d_y1, dy2, 2, mid, workspace=_wgrad_ws(st, d_y1, mid, dev))
-        _mark("bwd_conv2_dgrad")
-        if dy2s is not None and engine.wino_conv2_active(ws):
-            dy1 = _dgrad2_wino(engine, st, dy2s, w2)
-        else:
-            dy1 = ops.conv3x3_dgrad(dy2 if dy2s is None else dy2s, st.dgrad2, w2, 2)
-        if dy1.shape[1] != mid:
-            dy1 = dy1[:, :mid].contiguous()
-        del dy2, dy2s
-        dy1s = None
-        if y1_split:  # the masked dy1 also in the split layout: conv1's dgrad on the ring kernel
-            dy1s = torch.empty(ops.split_shape(B, mid, H, W), dtype=torch.bfloat16, device=dev)
-            ops.relu_backward_split_(dy1, ws.y1, dy1s)
-        else:
-            ops.relu_backward_(dy1, ws.y1)
+        dy1, dy1s, dw2, db2, dw3 = backward_to_dy1(engine, st, ws, w2, b2, w3, dmap)
         # conv1: db1 + coord channels, view channels (slab order through the pack's channel map)
         _mark("bwd_conv1_wgrad")
         nc = n * engine.C

@@ -13,6 +13,14 @@ autograd.  The 265 MB upsampled maps and the 620 MB concatenated slab of config 
 same-size final interpolate (``:81``, an exact identity) is elided.  There is no CPU fallback.
 
 Non-finite features or weights are outside the contract of the commuted order (see ``mvdet_amd.sum_head``).
+
+``ResProjVariant`` (``multiview_detector/models/res_proj_variant.py:15-84``) is the "late fusion" ablation: the
+ground plane sees only the warped FOOT channel of every view's image result (``img_res[:, 1]``, ``:72``) and the
+coord map, and ``map_classifier`` is ``PerspTransDetector``'s three 3x3 convs over ``num_cam + 2`` input channels
+(``:53-56``).  Same drop-in contract.  The planes are channel slices of ``imgs_result`` (views, not copies):
+warp + coord channels + conv1 + bias + ReLU are one HIP launch and conv2 / conv3 the engine's
+(``mvdet_amd.thin_fuse.ProjectThinFuse``), in inference and under autograd, where the planes' gradient joins the
+loss's own gradient of ``imgs_result`` on its way into the image head's backward.
 """
 from __future__ import annotations
 
@@ -21,6 +29,7 @@ import torch.nn as nn
 
 from .detector import _ViewsDetector
 from .sum_head import ProjectSumHead
+from .thin_fuse import ProjectThinFuse
 
 
 def view_gemm(feats, weight: torch.Tensor, n_views: int):
@@ -58,5 +67,32 @@ class NoJointConvVariant(_ViewsDetector):
         w_coord = first.weight[:, self._out_channel * self.num_cam:, 0, 0]  # the coord channels' columns (:76)
         map_result = self.head(zs, first.bias, w_coord, last.weight)
         if visualize:
+            self._show(torch.norm(map_result[0].detach(), dim=0))
+        return map_result, imgs_result
+
+
+class ResProjVariant(_ViewsDetector):
+    def __init__(self, dataset, arch: str = "resnet18", device=None, channels_last: bool = True,
+                 native_img_head: bool = True):
+        super().__init__()
+        self._init_views(dataset, arch, device, channels_last, native_img_head)
+        self.map_classifier = nn.Sequential(nn.Conv2d(self.num_cam + 2, 512, 3, padding=1), nn.ReLU(),
+                                            nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),
+                                            nn.Conv2d(512, 1, 3, padding=4, dilation=4, bias=False))  # :53-56
+        self._place()
+        self.head = ProjectThinFuse(self.proj_mats, tuple(self.upsample_shape), tuple(self.reducedgrid_shape))
+
+    def forward(self, imgs: torch.Tensor, visualize: bool = False):
+        B, N, C, H, W = imgs.shape
+        assert N == self.num_cam
+        if self._device.type != "cuda":
+            raise RuntimeError("ResProjVariant.forward needs a ROCm GPU (the hot path has no CPU fallback)")
+        _, imgs_result = self._views_forward(imgs, False)
+        planes = [r[:, 1:2] for r in imgs_result]  # head, *foot* (:72): views of the image results
+        c1, c2, c3 = self.map_classifier[0], self.map_classifier[2], self.map_classifier[4]
+        map_result = self.head(planes, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight)
+        if visualize:
+            for r in imgs_result:
+                self._show(r[0, 0].detach())
             self._show(torch.norm(map_result[0].detach(), dim=0))
         return map_result, imgs_result

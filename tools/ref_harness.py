@@ -98,3 +98,28 @@ def load_reference_no_joint_conv_variant():
     matplotlib.use("Agg")
     from multiview_detector.models.no_joint_conv_variant import NoJointConvVariant
     return NoJointConvVariant
+
+
+def load_reference_res_proj_variant():
+    """The reference's ``ResProjVariant`` (``tools/gen_golden_res_proj.py``).  Its file also imports
+    ``torchvision.models.alexnet`` and ``.mobilenet`` (never called with ``arch='resnet18'``): placeholder
+    modules stand in where torchvision is not installed."""
+    _install_stubs()
+    tv = sys.modules["torchvision"]
+    if not hasattr(tv, "__path__"):  # the stub package above, not the real torchvision
+        def _missing(name):
+            def fn(*a, **k):
+                raise RuntimeError(f"{name} is not available in the build container")
+            return fn
+
+        for mod, fn in (("alexnet", "alexnet"), ("mobilenet", "mobilenet_v2")):
+            m = types.ModuleType(f"torchvision.models.{mod}")
+            setattr(m, fn, _missing(fn))
+            setattr(tv.models, mod, m)
+            sys.modules[f"torchvision.models.{mod}"] = m
+    if REF_ROOT not in sys.path:
+        sys.path.insert(0, REF_ROOT)
+    import matplotlib
+    matplotlib.use("Agg")
+    from multiview_detector.models.res_proj_variant import ResProjVariant
+    return ResProjVariant

@@ -510,6 +510,15 @@ def check(status: int, what: str) -> None:
         raise NativeError(f"{what} failed: {msg} (status {status})")
 
 
+def backward_blocks(fn_name: str, *args) -> int:
+    """The block count a head's backward launches (``mvbev_*_backward_blocks``), which sizes its partial sums;
+    raises when the library answers that the launch cannot be made."""
+    blocks = int(getattr(load(), fn_name)(*args))
+    if blocks <= 0:
+        raise NativeError(f"{fn_name}: the grid does not fit one launch")
+    return blocks
+
+
 def strides4(t) -> "ctypes.Array":
     s = t.stride()
     if len(s) != 4:

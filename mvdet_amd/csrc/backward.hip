@@ -813,8 +813,8 @@ __global__ __launch_bounds__(kRedThreads) void bias_coord_grad_kernel(const floa
   __shared__ float tcx[kCoordTab], tcy[kCoordTab];
   const int co = blockIdx.x;
   if (dw) {
-    for (int i = threadIdx.x; i < W; i += kRedThreads) tcx[i] = (float)((double)i / (double)(W - 1) * 2.0 - 1.0);
-    for (int i = threadIdx.x; i < H; i += kRedThreads) tcy[i] = (float)((double)i / (double)(H - 1) * 2.0 - 1.0);
+    for (int i = threadIdx.x; i < W; i += kRedThreads) tcx[i] = coord_value(i, W);
+    for (int i = threadIdx.x; i < H; i += kRedThreads) tcy[i] = coord_value(i, H);
     __syncthreads();
   }
   float v[19];
@@ -1992,9 +1992,7 @@ int mvbev_warp_views_backward_f32(const mvbev_warp_view* views, int nviews, int6
     const mvbev_warp_view& v = views[i];
     if (!v.src || !v.dst) return MVBEV_ERR_NULL;
     if (v.dst_strides[3] != 1) return MVBEV_ERR_STRIDE;
-    a.v[i] = WarpView{v.src, v.src_strides[0], v.src_strides[1], v.src_strides[2], v.src_strides[3],
-                      v.dst, v.dst_strides[0], v.dst_strides[1], v.dst_strides[2], nullptr, {}};
-    for (int j = 0; j < 9; ++j) a.v[i].m[j] = v.m[j];
+    unpack_view(v, a.v[i]);
   }
   a.nviews = nviews;
   a.B = (int)B; a.C = (int)C; a.H = (int)H; a.W = (int)W; a.Ho = (int)Ho; a.Wo = (int)Wo;

@@ -31,6 +31,9 @@ __device__ inline int xcd_remap(int b, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
 
+// ReLU that keeps NaN (fmaxf would drop it)
+__device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
+
 template <typename T> __device__ inline float to_f32(T v);
 template <> __device__ inline float to_f32<float>(float v) { return v; }
 template <> __device__ inline float to_f32<__half>(__half v) { return __half2float(v); }

@@ -35,6 +35,7 @@
 //   channels per step with independent accumulators (memory-level parallelism), wave-uniform
 //   (scalar) weight loads; partial sums reduced through LDS.
 #include "common.h"
+#include "warp_common.h"
 
 namespace mvbev {
 
@@ -467,8 +468,8 @@ __global__ __launch_bounds__(256) void coord_term_kernel(const float* __restrict
   for (int k = 0; k < 3; ++k) {
     const int qq = q + k - 1, rr = r + k - 1;
     const bool cv = qq >= 0 && qq < W, rv = rr >= 0 && rr < H;
-    const float x = (float)((double)qq / (double)(W - 1) * 2.0 - 1.0);
-    const float y = (float)((double)rr / (double)(H - 1) * 2.0 - 1.0);
+    const float x = coord_value(qq, W);
+    const float y = coord_value(rr, H);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       xv[j][k] = (cv && r + j - 1 >= 0 && r + j - 1 < H) ? x : 0.f;  // tap (ky = j, kx = k)

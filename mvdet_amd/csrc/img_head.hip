@@ -55,9 +55,6 @@ struct IhBwdArgs {
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-// ReLU that keeps NaN (fmaxf would drop it)
-__device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
-
 // The upsampled pre-activation from its four taps, with the roundings of torch's GPU upsample
 // (UpSampleBilinear2d.cu): h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d) as the device compiler fuses it
 // there, written out with fmaf so that no compiler choice can move a rounding.  torch has two kernels and

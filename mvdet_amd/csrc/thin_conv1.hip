@@ -50,8 +50,6 @@ struct TcArgs {
   int Cout, cslices, split;
 };
 
-__device__ __forceinline__ float tc_relu_nan(float x) { return x < 0.f ? 0.f : x; }
-
 // mvbev_warp_perspective_f32's sample of plane `base` (row stride sH, column stride 1) at output pixel (u, v)
 __device__ inline float tc_sample(const float* __restrict__ base, int64_t sH, const float (&m)[9], int u, int v, int Ho,
                                   int Wo, int H, int W, bool& live) {
@@ -118,9 +116,9 @@ __global__ __launch_bounds__(kTcThreads) void thin_conv1_fwd_kernel(const TcArgs
         if (xwp && cs == 0 && hr >= 1 && hr <= kTcTH && hc >= 1 && hc <= kTcTW)
           xwp[(((int64_t)b * N + c) * Ho + r) * Wo + u] = val;
       } else if (c == N) {  // mvbev_fill_coord_map_f32's values
-        val = (float)((double)u / (double)(Wo - 1) * 2.0 - 1.0);
+        val = coord_value(u, Wo);
       } else {
-        val = (float)((double)r / (double)(Ho - 1) * 2.0 - 1.0);
+        val = coord_value(r, Ho);
       }
     }
     xs[c][hr][hc] = val;
@@ -161,7 +159,7 @@ __global__ __launch_bounds__(kTcThreads) void thin_conv1_fwd_kernel(const TcArgs
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = (acc2[j].x + acc2[j].y) + acc1[j];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = tc_relu_nan(acc[j]);
+    for (int j = 0; j < 8; ++j) acc[j] = relu_nan(acc[j]);
     if (!pix) continue;
     if (ta.split) {
       u32x4_t* out = static_cast<u32x4_t*>(y1) + 2 * (((int64_t)b * (ta.Cout / 8) + co0 / 8) * npix + (int64_t)r * Wo + u);
@@ -355,8 +353,8 @@ int mvbev_thin_conv1_forward_f32(const mvbev_warp_view* views, int nviews, int64
     if (!s.src) return MVBEV_ERR_NULL;
     if (s.src_strides[3] != 1 || s.src_strides[0] < 0 || s.src_strides[2] < 0) return MVBEV_ERR_STRIDE;
     WarpView& d = a.v[i];
-    d.src = s.src; d.sB = s.src_strides[0]; d.sC = 0; d.sH = s.src_strides[2]; d.sW = 1;
-    for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    unpack_view(s, d, false);  // (sW == 1: checked above)
+    d.sC = 0;
   }
   const int64_t tiles_x = ceil_div(Wo, (int64_t)kTcTW), tiles_y = ceil_div(Ho, (int64_t)kTcTH);
   const int64_t cslices = ceil_div(Cout, (int64_t)kTcCoutBlock);

@@ -615,11 +615,7 @@ static int warp_views(const mvbev_warp_view* views, int nviews, int64_t B, int64
     if (!s.src || !s.dst) return MVBEV_ERR_NULL;
     if (s.dst_strides[3] != 1) return MVBEV_ERR_STRIDE;
     WarpView& d = a.v[i];
-    d.src = s.src; d.sB = s.src_strides[0]; d.sC = s.src_strides[1];
-    d.sH = s.src_strides[2]; d.sW = s.src_strides[3];
-    d.dst = s.dst; d.dB = s.dst_strides[0]; d.dC = s.dst_strides[1]; d.dH = s.dst_strides[2];
-    d.m_dev = nullptr;
-    for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    unpack_view(s, d);
     d.row0 = row0s ? row0s[i] : 0;
     if (d.row0 < 0 || d.row0 + (out_rows ? out_rows : Ho) > Ho) return MVBEV_ERR_SHAPE;
   }
@@ -687,8 +683,8 @@ __global__ void coord_map_kernel(float* dst, int64_t dB, int64_t dC, int64_t dH,
   if (p >= Ho * Wo) return;
   const int v = p / Wo, u = p - v * Wo;
   float* o = dst + (int64_t)blockIdx.y * dB + (int64_t)v * dH + u;
-  o[0] = (float)((double)u / (double)(Wo - 1) * 2.0 - 1.0);
-  o[dC] = (float)((double)v / (double)(Ho - 1) * 2.0 - 1.0);
+  o[0] = coord_value(u, Wo);
+  o[dC] = coord_value(v, Ho);
 }
 
 // a gated zero fill (ABI 11900): 16-B stores over n16 units when *gate == tag, else nothing — the band
@@ -868,8 +864,7 @@ int mvbev_warp_wino_boxes(const mvbev_warp_view* views, int nviews, int64_t H, i
   if (nviews > kWarpMaxViews || 3 * r3_rows < Ho || H >= (1 << 29) || W >= (1 << 29)) return MVBEV_ERR_SHAPE;
   if (reinterpret_cast<uintptr_t>(boxes) & 15) return MVBEV_ERR_ALIGN;
   WarpArgs a = {};
-  for (int i = 0; i < nviews; ++i)
-    for (int q = 0; q < 9; ++q) a.v[i].m[q] = views[i].m[q];
+  for (int i = 0; i < nviews; ++i) unpack_view(views[i], a.v[i], false);  // (only the matrices are read)
   a.nviews = nviews;
   a.H = (int)H, a.W = (int)W, a.Ho = (int)Ho, a.Wo = (int)Wo;
   a.tiles_x = (int)ceil_div(Wo, kWwCols);
@@ -902,11 +897,7 @@ int mvbev_warp_views_wino_rows_ex(const mvbev_warp_view* views, int nviews, int6
     if (s.dst_strides[3] != 1) return MVBEV_ERR_STRIDE;
     if (s.dst_strides[2] != Wo) return MVBEV_ERR_STRIDE;  // a T row = its hi plane [Wo] then its lo plane
     WarpView& d = a.v[i];
-    d.src = s.src; d.sB = s.src_strides[0]; d.sC = s.src_strides[1];
-    d.sH = s.src_strides[2]; d.sW = s.src_strides[3];
-    d.dst = s.dst; d.dB = s.dst_strides[0]; d.dC = s.dst_strides[1]; d.dH = s.dst_strides[2];
-    d.m_dev = nullptr;
-    for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    unpack_view(s, d);
     pair = pair && d.sW == 1;
   }
   a.nviews = nviews;
@@ -969,8 +960,7 @@ int mvbev_warp_tile_mask(const mvbev_warp_view* views, int nviews, int64_t H, in
     return MVBEV_ERR_RANK;
   if (nviews > 32 || nviews > kWarpMaxViews || row0 < 0 || row0 + rows > Ho) return MVBEV_ERR_SHAPE;
   WarpArgs a = {};
-  for (int i = 0; i < nviews; ++i)
-    for (int k = 0; k < 9; ++k) a.v[i].m[k] = views[i].m[k];
+  for (int i = 0; i < nviews; ++i) unpack_view(views[i], a.v[i], false);  // (only the matrices are read)
   a.nviews = nviews;
   a.H = (int)H; a.W = (int)W; a.Ho = (int)Ho; a.Wo = (int)Wo;
   const int tiles_x = (int)ceil_div(Wo, tile_w);
@@ -989,8 +979,7 @@ int mvbev_warp_nonfinite_views(const mvbev_warp_view* views, int nviews, int64_t
   if (nviews <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return MVBEV_ERR_RANK;
   if (nviews > kWarpMaxViews || Ho * Wo > INT32_MAX) return MVBEV_ERR_SHAPE;
   WarpArgs a = {};
-  for (int i = 0; i < nviews; ++i)
-    for (int k = 0; k < 9; ++k) a.v[i].m[k] = views[i].m[k];
+  for (int i = 0; i < nviews; ++i) unpack_view(views[i], a.v[i], false);  // (only the matrices are read)
   a.nviews = nviews;
   a.H = (int)H; a.W = (int)W; a.Ho = (int)Ho; a.Wo = (int)Wo;
   hipLaunchKernelGGL(nonfinite_views_kernel, dim3(1), dim3(1024), 0, as_stream(stream), a, bits);

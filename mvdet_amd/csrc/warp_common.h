@@ -55,6 +55,22 @@ struct WarpView {
   int row0;            // grid row of dst row 0 (a row window of the grid: warp_tile_kernel, the exact warp)
 };
 
+// The copy of one ABI view into the kernels' WarpView and nothing else: every entry point makes its own null and
+// stride checks first.  with_dst = false: the source and the matrix only (entry points that write no per-view
+// destination, or that read nothing but the matrix).
+inline void unpack_view(const mvbev_warp_view& s, WarpView& d, bool with_dst = true) {
+  d.src = s.src; d.sB = s.src_strides[0]; d.sC = s.src_strides[1];
+  d.sH = s.src_strides[2]; d.sW = s.src_strides[3];
+  for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+  if (!with_dst) return;
+  d.dst = s.dst; d.dB = s.dst_strides[0]; d.dC = s.dst_strides[1]; d.dH = s.dst_strides[2];
+  d.m_dev = nullptr;
+}
+
+// The coord map's value at index i of an axis of n pixels (create_coord_map; mvbev_fill_coord_map_f32's values):
+// one definition for every kernel that writes, reads or differentiates the coord channels.
+__device__ __forceinline__ float coord_value(int i, int n) { return (float)((double)i / (double)(n - 1) * 2.0 - 1.0); }
+
 // n / d for 0 <= n < 2^31 as (umulhi(n, m) + n) >> s (round 6: the fused warps' block decomposition took four
 // runtime divisions, ~100 scalar instructions of the ~295 each wave issued at cfg3); m == 0: not set (plain division)
 struct FastDiv {

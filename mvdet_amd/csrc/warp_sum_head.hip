@@ -50,7 +50,6 @@ struct ShArgs {
   int hidden_vec;     // 16-B hidden stores (Wo % 4 == 0, aligned base)
 };
 
-__device__ __forceinline__ float sh_relu_nan(float x) { return x < 0.f ? 0.f : x; }
 __device__ __forceinline__ float sh_lanef(float x, int lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane));
 }
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(kWave) void warp_sum_head_fwd_kernel(const ShArgs s
       pc0[k][j] = ok ? sa.w_coord[2 * c] : 0.f;
       pc1[k][j] = ok ? sa.w_coord[2 * c + 1] : 0.f;
     }
-  const float cy = (float)((double)v / (double)(Ho - 1) * 2.0 - 1.0);  // mvbev_fill_coord_map_f32's values
+  const float cy = coord_value(v, Ho);  // mvbev_fill_coord_map_f32's values
 
   // geometry role of this lane: view gview of the group's pixel gpx
   const int gview = lane & 15, gpx = lane >> 4;
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(kWave) void warp_sum_head_fwd_kernel(const ShArgs s
           }
         }
       }
-      const float cx = (float)((double)u / (double)(Wo - 1) * 2.0 - 1.0);
+      const float cx = coord_value(u, Wo);
       float part = 0.f;
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
@@ -170,7 +169,7 @@ __global__ __launch_bounds__(kWave) void warp_sum_head_fwd_kernel(const ShArgs s
         for (int j = 0; j < 4; ++j) {
           float pre = acc[k][j] + fmaf(pc1[k][j], cy, fmaf(pc0[k][j], cx, pb[k][j]));
           if (nan) pre = __builtin_nanf("");
-          hv[j] = sh_relu_nan(pre);
+          hv[j] = relu_nan(pre);
           part = fmaf(hv[j], pw[k][j], part);  // (channels >= Cm: all-zero parameters, hv = 0)
         }
         if (sa.hidden)
@@ -230,6 +229,7 @@ __global__ __launch_bounds__(kShBwdThreads) void warp_sum_head_bwd_kernel(const 
   auto one = [&](int p, float hv, float g) __attribute__((always_inline)) {
     const float d = hv <= 0.f ? 0.f : g * wc;
     const int y = p / a.Wo, x = p - y * a.Wo;
+    // (not coord_value: the reciprocal multiply can round differently, and changing it changes the gradients)
     const float cx = (float)((double)x * ix * 2.0 - 1.0), cy = (float)((double)y * iy * 2.0 - 1.0);
     s[0] = fmaf(g, hv, s[0]);
     s[1] += d;
@@ -322,8 +322,7 @@ int mvbev_warp_sum_head_forward_f32(const mvbev_warp_view* views, int nviews, in
     if (s.src_strides[1] != 1 || s.src_strides[0] < 0 || s.src_strides[2] < 0 || s.src_strides[3] < 0)
       return MVBEV_ERR_STRIDE;  // channels-last lines
     WarpView& d = a.v[i];
-    d.src = s.src; d.sB = s.src_strides[0]; d.sC = 1; d.sH = s.src_strides[2]; d.sW = s.src_strides[3];
-    for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    unpack_view(s, d, false);  // (sC == 1: checked above)
     if (Cm % 4 == 0 && d.sB % 4 == 0 && d.sH % 4 == 0 && d.sW % 4 == 0 && (reinterpret_cast<uintptr_t>(d.src) & 15) == 0)
       sa.vec_mask |= 1u << i;
   }

@@ -663,11 +663,7 @@ static int warp_exact(const mvbev_warp_view* views, const int32_t* row0s, int nv
     if (!s.src || !s.dst) return MVBEV_ERR_NULL;
     if (s.dst_strides[3] != 1) return MVBEV_ERR_STRIDE;
     WarpView& d = a.v[i];
-    d.src = s.src; d.sB = s.src_strides[0]; d.sC = s.src_strides[1];
-    d.sH = s.src_strides[2]; d.sW = s.src_strides[3];
-    d.dst = s.dst; d.dB = s.dst_strides[0]; d.dC = s.dst_strides[1]; d.dH = s.dst_strides[2];
-    d.m_dev = nullptr;
-    for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    unpack_view(s, d);
     d.row0 = row0s ? row0s[i] : 0;
     if (d.row0 < 0 || d.row0 + orows > Ho) return MVBEV_ERR_SHAPE;
   }
@@ -733,8 +729,7 @@ extern "C" int mvbev_warp_upsampled_wino_boxes(const mvbev_warp_view* views, int
   if (reinterpret_cast<uintptr_t>(boxes) & 15) return MVBEV_ERR_ALIGN;
   UpArgs ua = {};
   WarpArgs& a = ua.w;
-  for (int i = 0; i < nviews; ++i)
-    for (int q = 0; q < 9; ++q) a.v[i].m[q] = views[i].m[q];
+  for (int i = 0; i < nviews; ++i) unpack_view(views[i], a.v[i], false);  // (only the matrices are read)
   a.nviews = nviews;
   a.H = (int)H, a.W = (int)W, a.Ho = (int)Ho, a.Wo = (int)Wo;
   a.tiles_x = (int)ceil_div(Wo, kWcCols);
@@ -770,12 +765,7 @@ extern "C" int mvbev_warp_views_upsampled_wino_rows_ex(const mvbev_warp_view* vi
     const mvbev_warp_view& s = views[i];
     if (!s.src || !s.dst) return MVBEV_ERR_NULL;
     if (s.dst_strides[3] != 1) return MVBEV_ERR_STRIDE;
-    WarpView& d = a.v[i];
-    d.src = s.src; d.sB = s.src_strides[0]; d.sC = s.src_strides[1];
-    d.sH = s.src_strides[2]; d.sW = s.src_strides[3];
-    d.dst = s.dst; d.dB = s.dst_strides[0]; d.dC = s.dst_strides[1]; d.dH = s.dst_strides[2];
-    d.m_dev = nullptr;
-    for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    unpack_view(s, a.v[i]);
   }
   a.nviews = nviews;
   a.skip_zero = (flags & MVBEV_WARP_DST_ZEROED) != 0;
@@ -848,12 +838,7 @@ extern "C" int mvbev_warp_views_upsampled_ex(const mvbev_warp_view* views, int n
     if (!s.src || !s.dst) return MVBEV_ERR_NULL;
     if (s.dst_strides[3] != 1) return MVBEV_ERR_STRIDE;
     if (s.dst_strides[2] != Wo) return MVBEV_ERR_STRIDE;  // a T row = its hi plane [Wo] then its lo plane
-    WarpView& d = a.v[i];
-    d.src = s.src; d.sB = s.src_strides[0]; d.sC = s.src_strides[1];
-    d.sH = s.src_strides[2]; d.sW = s.src_strides[3];
-    d.dst = s.dst; d.dB = s.dst_strides[0]; d.dC = s.dst_strides[1]; d.dH = s.dst_strides[2];
-    d.m_dev = nullptr;
-    for (int k = 0; k < 9; ++k) d.m[k] = s.m[k];
+    unpack_view(s, a.v[i]);
   }
   a.nviews = nviews;
   a.skip_zero = (flags & MVBEV_WARP_DST_ZEROED) != 0;

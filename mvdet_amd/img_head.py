@@ -20,8 +20,8 @@ import torch
 
 from . import _native
 from .ops import _stream
+from .rig import MAX_VIEWS, check_views
 
-MAX_VIEWS = 16  # kIhMaxViews (csrc/img_head.hip)
 MAX_CM = 256    # kIhMaxCm
 MAX_CO = 4      # kIhMaxCo
 
@@ -34,28 +34,9 @@ def supported(n_views: int, g_shape, co: int, size) -> bool:
 
 
 def _check(gs, weight, size):
-    if isinstance(gs, torch.Tensor) or not hasattr(gs, "__len__"):
-        raise TypeError(f"gs must be a sequence of tensors, got {type(gs).__name__}")
-    if not 0 < len(gs) <= MAX_VIEWS:
-        raise ValueError(f"1 .. {MAX_VIEWS} views per call, got {len(gs)}")
-    for name, t in [(f"gs[{i}]", g) for i, g in enumerate(gs)] + [("weight", weight)]:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    check_views("gs", gs, "the image head", None, [("weight", weight)],
+                lambda g: None if g.dim() == 4 else f"4-D [B,Cm,h,w], got {g.dim()}-D", params_on_device=False)
     g0 = gs[0]
-    for i, g in enumerate(gs):
-        if g.dim() != 4:
-            raise ValueError(f"gs[{i}] must be 4-D [B,Cm,h,w], got {g.dim()}-D")
-        if g.shape != g0.shape:
-            raise ValueError(f"gs[{i}] {tuple(g.shape)} differs from gs[0] {tuple(g0.shape)}")
-    for i, g in enumerate(gs):
-        if not g.is_cuda:
-            raise ValueError(f"gs[{i}] is on {g.device}: the image head runs on a ROCm GPU only (no CPU fallback)")
-        if g.device != g0.device:
-            raise ValueError(f"gs[{i}] is on {g.device}, gs[0] on {g0.device}")
-    if min(g0.shape) == 0:
-        raise ValueError(f"empty gs[0] {tuple(g0.shape)}")
     if not (weight.dim() == 2 or (weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1))):
         raise ValueError(f"weight must be [Co,Cm] or [Co,Cm,1,1], got {tuple(weight.shape)}")
     if weight.shape[1] != g0.shape[1]:
@@ -132,9 +113,7 @@ class UpsampleReluConv1x1(torch.autograd.Function):
             return (None, None) + tuple(grads)
         partials, blocks = None, 0
         if want_w:
-            blocks = int(lib.mvbev_img_head_backward_blocks(items, n, *dims))
-            if blocks <= 0:
-                raise _native.NativeError("mvbev_img_head_backward_blocks: the views do not fit one launch")
+            blocks = _native.backward_blocks("mvbev_img_head_backward_blocks", items, n, *dims)
             partials = torch.empty(co * cm * blocks, dtype=torch.float32, device=dev)
         stream = _stream(w2)
         _native.check(lib.mvbev_img_head_backward_f32(items, n, *dims, w2.data_ptr(),

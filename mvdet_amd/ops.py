@@ -37,6 +37,49 @@ def _stream(t: torch.Tensor) -> int:
     return _native.stream_ptr(t.device)
 
 
+# an empty slot's matrix: a finite map far outside the source (its warp is zero everywhere, its mask bit stays clear)
+_EMPTY_SLOT = (0.0, 0.0, 1e6, 0.0, 0.0, 1e6, 0.0, 0.0, 1.0)
+
+
+def _m9(m):
+    """A host [3,3] kornia matrix as the ABI's ``float[9]``; None: an empty slot."""
+    return (ctypes.c_float * 9)(*(_EMPTY_SLOT if m is None else
+                                  torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()))
+
+
+def _split_dst_strides(d: torch.Tensor, want_shape) -> Tuple[int, int, int, int]:
+    """The ABI strides (32-byte units) of a split-bf16 blocked destination [B, G, H, W, 2, 8] whose pixel entries
+    (bf16 hi[8] then lo[8]) are contiguous; raises for anything else."""
+    if tuple(d.shape) != tuple(want_shape) or d.dtype != torch.bfloat16 or d.stride(5) != 1 or d.stride(4) != KC or \
+            d.stride(3) != 2 * KC:
+        raise ValueError(f"split dst must be a bf16 {tuple(want_shape)} tensor with contiguous pixels")
+    return (d.stride(0) // 16, d.stride(1) // 16, d.stride(2) // 16, 1)
+
+
+def _view_table(srcs, m_norms, dsts=None, dst_strides=None, unit_dim: Optional[int] = None):
+    """The ``mvbev_warp_view`` table of one call, one entry per view (nothing is cached: the pointers change every
+    frame).  ``srcs``: the source tensors, or None for a table of matrices alone; ``m_norms[i]``: as ``_m9`` (None
+    for the whole argument: the entry point reads no matrix); ``dsts[i]``: a tensor or a device address, with
+    ``dst_strides[i]`` in the entry point's ABI units (default: the tensor's own strides); ``unit_dim``: a source
+    dimension of size 1 whose stride is passed as 1 (torch reports any stride for it)."""
+    n = len(m_norms) if srcs is None else len(srcs)
+    arr = (_native.WarpView * n)()
+    for i in range(n):
+        v = arr[i]
+        if srcs is not None:
+            st = list(srcs[i].stride())
+            if unit_dim is not None:
+                st[unit_dim] = 1
+            v.src, v.src_strides = srcs[i].data_ptr(), _native._i64x4(*st)
+        if dsts is not None:
+            d = dsts[i]
+            v.dst = d.data_ptr() if isinstance(d, torch.Tensor) else d
+            v.dst_strides = _native._i64x4(*(d.stride() if dst_strides is None else dst_strides[i]))
+        if m_norms is not None:
+            v.m = _m9(m_norms[i])
+    return arr
+
+
 # ----------------------------------------------------------------------------------------------
 # warp
 
@@ -123,21 +166,17 @@ def warp_views_upsampled_into(srcs, up_hw, m_norms, dsts, split: bool = False, d
     dtype = srcs[0].dtype
     Ho, Wo = dsts[0].shape[2], dsts[0].shape[3]
     want = split_shape(B, C, Ho, Wo) if split else (B, C, Ho, Wo)
-    arr = (_native.WarpView * n)()
-    for i, (s, m, d) in enumerate(zip(srcs, m_norms, dsts)):
+    dstrs = []
+    for s, d in zip(srcs, dsts):
         if tuple(s.shape) != (B, C, h, w) or tuple(d.shape) != want or s.dtype != dtype:
             raise ValueError(f"all views must share shapes/dtype: src {tuple(s.shape)} dst {tuple(d.shape)}")
         if split:
-            if d.dtype != torch.bfloat16 or d.stride(5) != 1 or d.stride(4) != KC or d.stride(3) != 2 * KC:
-                raise ValueError("split dst must be a bf16 [B,G,Ho,Wo,2,8] tensor with contiguous pixels")
-            dstr = (d.stride(0) // 16, d.stride(1) // 16, d.stride(2) // 16, 1)
+            dstrs.append(_split_dst_strides(d, want))
         else:
             if d.dtype != torch.float32 or dtype != torch.float32:
                 raise TypeError("the fp32-output fused warp takes fp32 sources and destinations")
-            dstr = tuple(d.stride())
-        mm = torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i] = _native.WarpView(s.data_ptr(), (ctypes.c_int64 * 4)(*s.stride()), d.data_ptr(),
-                                  (ctypes.c_int64 * 4)(*dstr), (ctypes.c_float * 9)(*mm))
+            dstrs.append(d.stride())
+    arr = _view_table(srcs, m_norms, dsts, dstrs)
     if dtype not in (torch.float32, torch.float16):
         raise TypeError(f"unsupported dtype {dtype}")
     lib = _native.load()
@@ -173,23 +212,19 @@ def warp_views_into(srcs, m_norms, dsts, split: bool = False, C: Optional[int] =
     else:
         Ho, Wo = dsts[0].shape[2], dsts[0].shape[3]
         want = (B, C, Ho, Wo)
-    arr = (_native.WarpView * n)()
-    for i, (s, m, d) in enumerate(zip(srcs, m_norms, dsts)):
+    dstrs = []
+    for s, d in zip(srcs, dsts):
         if tuple(s.shape) != (B, C, H, W) or tuple(d.shape) != want:
             raise ValueError(f"all views must share shapes: src {tuple(s.shape)} dst {tuple(d.shape)} want {want}")
         if s.dtype != dtype:
             raise TypeError("all views must share one dtype")
         if split:
-            if d.dtype != torch.bfloat16 or d.stride(5) != 1 or d.stride(4) != KC or d.stride(3) != 2 * KC:
-                raise ValueError("split dst must be a bf16 [B,G,Ho,Wo,2,8] tensor with contiguous pixels")
-            dstr = (d.stride(0) // 16, d.stride(1) // 16, d.stride(2) // 16, 1)  # 32-byte units
+            dstrs.append(_split_dst_strides(d, want))
         else:
             if d.dtype != dtype:
                 raise TypeError("dst dtype must match src")
-            dstr = tuple(d.stride())
-        mm = torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i] = _native.WarpView(s.data_ptr(), (ctypes.c_int64 * 4)(*s.stride()), d.data_ptr(),
-                                  (ctypes.c_int64 * 4)(*dstr), (ctypes.c_float * 9)(*mm))
+            dstrs.append(d.stride())
+    arr = _view_table(srcs, m_norms, dsts, dstrs)
     lib = _native.load()
     if split:
         if dtype not in (torch.float32, torch.float16):
@@ -307,15 +342,12 @@ def warp_views_exact_into(srcs, m_norms, dsts, up_hw=None, gate=None, row0s=None
     Ho = rows if grid_rows is None else int(grid_rows)
     if row0s is None and grid_rows is not None and grid_rows != rows:
         raise ValueError("a row window needs row0s")
-    arr = (_native.WarpView * n)()
-    for i, (s_, m, d) in enumerate(zip(srcs, m_norms, dsts)):
+    for s_, d in zip(srcs, dsts):
         if tuple(s_.shape) != (B, C, h, w) or s_.dtype != dtype or dtype not in (torch.float32, torch.float16):
             raise ValueError("all views must be fp32 (or fp16) [B,C,h,w] of one shape and dtype")
         if tuple(d.shape) != (B, C, rows, Wo) or d.dtype != torch.float32 or d.stride(3) != 1:
             raise ValueError(f"dst must be an fp32 [{B},{C},{rows},{Wo}] view with unit column stride")
-        mm = torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i] = _native.WarpView(s_.data_ptr(), (ctypes.c_int64 * 4)(*s_.stride()), d.data_ptr(),
-                                  (ctypes.c_int64 * 4)(*d.stride()), (ctypes.c_float * 9)(*mm))
+    arr = _view_table(srcs, m_norms, dsts)
     gp, gt = _gate(gate)
     lib = _native.load()
     if row0s is None and dtype == torch.float32:
@@ -348,17 +380,10 @@ def warp_views_split_rows_into(srcs, m_norms, dsts, row0s, grid_rows: int, dst_z
         raise TypeError(f"unsupported dtype {dtype}")
     rows, Wo = dsts[0].shape[2], dsts[0].shape[3]
     want = split_shape(B, C, rows, Wo)
-    arr = (_native.WarpView * n)()
-    for i, (s_, m, d) in enumerate(zip(srcs, m_norms, dsts)):
+    for s_ in srcs:
         if tuple(s_.shape) != (B, C, H, W) or s_.dtype != dtype:
             raise ValueError("all views must share one shape and dtype")
-        if tuple(d.shape) != want or d.dtype != torch.bfloat16 or d.stride(5) != 1 or d.stride(4) != KC or \
-                d.stride(3) != 2 * KC:
-            raise ValueError(f"split dst must be a bf16 {want} tensor with contiguous pixels")
-        mm = torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i] = _native.WarpView(s_.data_ptr(), (ctypes.c_int64 * 4)(*s_.stride()), d.data_ptr(),
-                                  (ctypes.c_int64 * 4)(d.stride(0) // 16, d.stride(1) // 16, d.stride(2) // 16, 1),
-                                  (ctypes.c_float * 9)(*mm))
+    arr = _view_table(srcs, m_norms, dsts, [_split_dst_strides(d, want) for d in dsts])
     r0 = (ctypes.c_int32 * n)(*[int(r) for r in row0s])
     fp, ft = _gate(nonfinite)
     st = _native.load().mvbev_warp_views_split_bf16_rows(arr, r0, n, int(dtype == torch.float16), B, C, H, W,
@@ -395,11 +420,7 @@ def store_gated_(src: torch.Tensor, dst: torch.Tensor, gate) -> torch.Tensor:
         raise ValueError("src must be an fp32 [B, C, H, W] view with unit column stride")
     B, C, H, W = src.shape
     if dst.dtype == torch.bfloat16:
-        if tuple(dst.shape) != split_shape(B, C, H, W) or dst.stride(5) != 1 or dst.stride(4) != KC or \
-                dst.stride(3) != 2 * KC:
-            raise ValueError(f"split dst must be a [B, G, H, W, 2, 8] view of {split_shape(B, C, H, W)} with "
-                             "contiguous pixels")
-        layout, dstr = _native.LAYOUT_SPLIT_BF16, (dst.stride(0) // 16, dst.stride(1) // 16, dst.stride(2) // 16, 1)
+        layout, dstr = _native.LAYOUT_SPLIT_BF16, _split_dst_strides(dst, split_shape(B, C, H, W))
     elif dst.dtype == torch.float32 and tuple(dst.shape) == (B, C, H, W) and dst.stride(3) == 1:
         layout, dstr = _native.LAYOUT_F32, tuple(dst.stride())
     else:
@@ -443,14 +464,12 @@ def to_channels_last_into(srcs, dsts) -> list:
         raise ValueError("need 1..16 matching srcs / dsts")
     _require_cuda(*srcs, *dsts)
     B, C, H, W = srcs[0].shape
-    arr = (_native.WarpView * n)()
-    for i, (s_, d) in enumerate(zip(srcs, dsts)):
+    for s_, d in zip(srcs, dsts):
         if tuple(s_.shape) != (B, C, H, W) or s_.dtype != torch.float32:
             raise ValueError("all views must be fp32 [B,C,H,W] of one shape")
         if tuple(d.shape) != (B, H, W, C) or d.dtype != torch.float32 or not d.is_contiguous():
             raise ValueError(f"dst must be a contiguous fp32 [{B},{H},{W},{C}] tensor")
-        arr[i] = _native.WarpView(s_.data_ptr(), (ctypes.c_int64 * 4)(*s_.stride()), d.data_ptr(),
-                                  (ctypes.c_int64 * 4)(0, 0, 0, 1), (ctypes.c_float * 9)())
+    arr = _view_table(srcs, None, dsts, [(0, 0, 0, 1)] * n)
     st = _native.load().mvbev_nchw_to_nhwc_f32(arr, n, B, C, H, W, _stream(dsts[0]))
     _native.check(st, "mvbev_nchw_to_nhwc_f32")
     return [d.permute(0, 3, 1, 2) for d in dsts]
@@ -627,12 +646,7 @@ def warp_tile_mask(m_norms, src_hw, grid_hw, row0: int, rows: int, halo: int, de
     n = len(m_norms)
     if not 0 < n <= 16:
         raise ValueError("need 1..16 slots")
-    arr = (_native.WarpView * n)()
-    for i, m in enumerate(m_norms):
-        # an empty slot: a finite map far outside the source (bit stays clear)
-        mm = [0.0, 0.0, 1e6, 0.0, 0.0, 1e6, 0.0, 0.0, 1.0] if m is None else \
-            torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i].m = (ctypes.c_float * 9)(*mm)
+    arr = _view_table(None, m_norms)
     H, W = src_hw
     Ho, Wo = grid_hw
     tiles = -(-rows // tile_h) * -(-Wo // tile_w)
@@ -650,11 +664,7 @@ def warp_nonfinite_views(m_norms, src_hw, grid_hw, device) -> int:
     n = len(m_norms)
     if not 0 < n <= 16:
         raise ValueError("need 1..16 slots")
-    arr = (_native.WarpView * n)()
-    for i, m in enumerate(m_norms):
-        mm = [0.0, 0.0, 1e6, 0.0, 0.0, 1e6, 0.0, 0.0, 1.0] if m is None else \
-            torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i].m = (ctypes.c_float * 9)(*mm)
+    arr = _view_table(None, m_norms)
     H, W = src_hw
     Ho, Wo = grid_hw
     bits = torch.zeros(1, dtype=torch.int32, device=device)
@@ -855,9 +865,7 @@ def warp_wino_boxes(m_norms, src_hw, grid_hw, device, backbone_hw=None, form: in
         raise ValueError("need 1..16 views")
     lib = _native.load()
     boxes = torch.empty((n, int(lib.mvbev_warp_wino_boxes_count(Wo, r3)), 4), dtype=torch.int32, device=device)
-    arr = (_native.WarpView * n)()
-    for i, m in enumerate(m_norms):
-        arr[i].m = (ctypes.c_float * 9)(*torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist())
+    arr = _view_table(None, m_norms)
     if backbone_hw is not None:
         st = lib.mvbev_warp_upsampled_wino_boxes(arr, n, int(backbone_hw[0]), int(backbone_hw[1]), int(src_hw[0]),
                                                  int(src_hw[1]), Ho, Wo, r3, boxes.data_ptr(), _stream(boxes))
@@ -897,19 +905,14 @@ def warp_views_wino_rows_into(srcs, m_norms, t: torch.Tensor, slots, Cs: int, K:
         raise ValueError("t must be a contiguous bf16 buffer of wino_rows_bytes (form 4: wino43_rows_bytes)")
     if Cs % KC or C > Cs:
         raise ValueError("Cs must be a multiple of 8 holding C")
-    arr = (_native.WarpView * n)()
     dtype = srcs[0].dtype
     if dtype == torch.float16 and up_hw is not None:
         raise TypeError("the fused upsample warp takes fp32 backbone maps")
-    for i, (s_, m, slot) in enumerate(zip(srcs, m_norms, slots)):
+    for s_ in srcs:
         if tuple(s_.shape) != (B, C, H, W) or s_.dtype != dtype or dtype not in (torch.float32, torch.float16):
             raise ValueError("all views must be fp32 (or fp16: ABI 11900) [B,C,H,W] of one shape and dtype")
-        mm = torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i].src = s_.data_ptr()
-        arr[i].src_strides = _native._i64x4(*s_.stride())
-        arr[i].dst = t.data_ptr() + 32 * (int(slot) * (Cs // KC)) * nx * r3 * Wo
-        arr[i].dst_strides = _native._i64x4(K8 * nx * r3 * Wo, nx * r3 * Wo, Wo, 1)  # 32-byte units
-        arr[i].m = (ctypes.c_float * 9)(*mm)
+    arr = _view_table(srcs, m_norms, [t.data_ptr() + 32 * (int(slot) * (Cs // KC)) * nx * r3 * Wo for slot in slots],
+                      [(K8 * nx * r3 * Wo, nx * r3 * Wo, Wo, 1)] * n)  # 32-byte units
     flags = ((_native.WARP_DST_ZEROED if dst_zeroed else 0) | (_native.WARP_SRC_F16 if dtype == torch.float16 else 0)
              | (_native.WARP_WINO43 if form == 4 else 0))
     fp, ft = _gate(nonfinite)
@@ -1288,17 +1291,14 @@ def warp_views_backward(grad_outs, m_norms, grad_srcs) -> None:
     _require_cuda(*grad_outs, *grad_srcs)
     B, C, Ho, Wo = grad_outs[0].shape
     _, _, H, W = grad_srcs[0].shape
-    arr = (_native.WarpView * n)()
-    for i, (g, m, d) in enumerate(zip(grad_outs, m_norms, grad_srcs)):
+    for g, d in zip(grad_outs, grad_srcs):
         if tuple(g.shape) != (B, C, Ho, Wo) or tuple(d.shape) != (B, C, H, W):
             raise ValueError(f"all views must share shapes: grad_out {tuple(g.shape)} grad_src {tuple(d.shape)}")
         if g.dtype != torch.float32 or d.dtype != torch.float32:
             raise TypeError("the warp backward is fp32")
         if d.stride(3) != 1:
             raise ValueError("grad_src needs contiguous rows (innermost stride 1)")
-        mm = torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
-        arr[i] = _native.WarpView(g.data_ptr(), (ctypes.c_int64 * 4)(*g.stride()), d.data_ptr(),
-                                  (ctypes.c_int64 * 4)(*d.stride()), (ctypes.c_float * 9)(*mm))
+    arr = _view_table(grad_outs, m_norms, grad_srcs)
     st = _native.load().mvbev_warp_views_backward_f32(arr, n, B, C, H, W, Ho, Wo, _stream(grad_srcs[0]))
     _native.check(st, "mvbev_warp_views_backward_f32")
 
@@ -1314,7 +1314,7 @@ class WarpAdjointPlan:
         H, W = int(src_hw[0]), int(src_hw[1])
         Ho, Wo = int(grid_hw[0]), int(grid_hw[1])
         device = torch.device(device)
-        mm = (ctypes.c_float * 9)(*torch.as_tensor(m_norm, dtype=torch.float32).reshape(9).tolist())
+        mm = _m9(m_norm)
         lib = _native.load()
         if backbone_hw is None:
             self.src_hw, self.grid_hw, per = (H, W), (Ho, Wo), 4
@@ -1804,7 +1804,7 @@ class BevFuse:
         if backbone_hw is not None:
             g.h, g.w = (int(x) for x in backbone_hw)
         for v, m in enumerate(m_norms):
-            g.m[v] = (ctypes.c_float * 9)(*torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist())
+            g.m[v] = _m9(m)
         self.plan = _native.BevPlan()
         _native.check(_native.load().mvbev_bev_plan_init(ctypes.byref(g), ctypes.byref(self.plan)),
                       "mvbev_bev_plan_init")

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _native, ops
-from .geometry import kornia_src_norm_from_dst_norm
+from .rig import norm_matrices
 
 # halo rows each layer needs below/above its output rows (dilations 1, 2, 4 of :51-54)
 HALO_CONV1, HALO_CONV2, HALO_CONV3 = 1, 2, 4
@@ -161,9 +161,7 @@ class ProjectFuse:
             assert set(self.slot_of) <= set(range(self.num_cam)) and self.S > 0
         # kornia steps 1-2 (normalize_homography + _torch_inverse_cast) on the host, fp32,
         # from the fp32-cast projection matrix exactly as :68-69 feeds kornia.
-        self.m_norm_cpu = torch.stack([
-            kornia_src_norm_from_dst_norm(M.float().reshape(1, 3, 3), self.src_hw, self.grid_hw)[0]
-            for M in proj_mats])  # [N, 3, 3]
+        self.m_norm_cpu = norm_matrices(proj_mats, self.src_hw, self.grid_hw)  # [N, 3, 3]
         # conv1 weight channels, in slab order: slot s channel c -> module channel v*C + c (a part: its view's
         # channel c0 + c)
         chan_map = []

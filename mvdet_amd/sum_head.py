@@ -25,45 +25,19 @@ is NaN, as the reference's warp makes it).  Non-finite *features or weights* are
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _native, ops
-from .geometry import kornia_src_norm_from_dst_norm
 from .ops import _stream
+from .rig import MAX_VIEWS, Rig, check_views  # noqa: F401  (MAX_VIEWS: this module's public limit)
 
-MAX_VIEWS = 16  # kWarpMaxViews (csrc/warp_common.h)
 MAX_CM = 512    # kShMaxCm (csrc/warp_sum_head.hip)
 
 
 def _check(n_views, zs, bias, w_coord, w2):
-    if isinstance(zs, torch.Tensor) or not hasattr(zs, "__len__"):
-        raise TypeError(f"zs must be a sequence of tensors, got {type(zs).__name__}")
-    if not 0 < len(zs) <= MAX_VIEWS:
-        raise ValueError(f"1 .. {MAX_VIEWS} views per call, got {len(zs)}")
-    if len(zs) != n_views:
-        raise ValueError(f"{len(zs)} views for a head built for {n_views}")
-    named = [(f"zs[{i}]", z) for i, z in enumerate(zs)] + [("bias", bias), ("w_coord", w_coord), ("w2", w2)]
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-    z0 = zs[0]
-    for i, z in enumerate(zs):
-        if z.dim() != 4:
-            raise ValueError(f"zs[{i}] must be 4-D [B,Cm,h,w], got {z.dim()}-D")
-        if z.shape != z0.shape:
-            raise ValueError(f"zs[{i}] {tuple(z.shape)} differs from zs[0] {tuple(z0.shape)}")
-    for name, t in named:
-        if not t.is_cuda:
-            raise ValueError(f"{name} is on {t.device}: the warp-sum head runs on a ROCm GPU only (no CPU fallback)")
-        if t.device != z0.device:
-            raise ValueError(f"{name} is on {t.device}, zs[0] on {z0.device}")
-    if min(z0.shape) == 0:
-        raise ValueError(f"empty zs[0] {tuple(z0.shape)}")
-    cm = z0.shape[1]
+    check_views("zs", zs, "the warp-sum head", n_views, [("bias", bias), ("w_coord", w_coord), ("w2", w2)],
+                lambda z: None if z.dim() == 4 else f"4-D [B,Cm,h,w], got {z.dim()}-D")
+    cm = zs[0].shape[1]
     if cm > MAX_CM:
         raise ValueError(f"{cm} channels: the kernel takes Cm <= {MAX_CM}")
     if bias.numel() != cm or bias.dim() != 1:
@@ -99,12 +73,7 @@ class WarpSumHead(torch.autograd.Function):
         keep = need or return_hidden
         out = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=dev)
         hidden = torch.empty((B, cm, Ho, Wo), dtype=torch.float32, device=dev) if keep else None
-        arr = (_native.WarpView * n)()
-        for i, z in enumerate(lines):
-            st = list(z.stride())
-            st[1] = 1  # (a single channel: any stride torch reports)
-            arr[i].src, arr[i].src_strides = z.data_ptr(), (ctypes.c_int64 * 4)(*st)
-            arr[i].m = (ctypes.c_float * 9)(*head.m_norm_cpu[i].reshape(9).tolist())
+        arr = ops._view_table(lines, head.m_norm_cpu, unit_dim=1)  # (a single channel: any stride torch reports)
         pb, pc, pw = bias.detach().contiguous(), w_coord.detach().reshape(cm, 2).contiguous(), \
             w2.detach().reshape(cm).contiguous()
         boxes = head.boxes(dev, (h, w))
@@ -134,9 +103,7 @@ class WarpSumHead(torch.autograd.Function):
             dmap = dmap.to(device=dev, dtype=torch.float32).contiguous()
         stream = _stream(hidden)
         params = want_b or want_c or want_w
-        blocks = int(lib.mvbev_warp_sum_head_backward_blocks(B, cm, Ho, Wo))
-        if blocks <= 0:
-            raise _native.NativeError("mvbev_warp_sum_head_backward_blocks: the grid does not fit one launch")
+        blocks = _native.backward_blocks("mvbev_warp_sum_head_backward_blocks", B, cm, Ho, Wo)
         partials = torch.empty(4 * cm * blocks, dtype=torch.float32, device=dev) if params else None
         # (not in place over hidden: a caller may hold it, and the graph may be kept for a second backward)
         dhidden = torch.empty_like(hidden) if any(want_z) else None
@@ -166,7 +133,7 @@ class WarpSumHead(torch.autograd.Function):
         return (None, None, gb, gc, gw) + tuple(gz)
 
 
-class ProjectSumHead:
+class ProjectSumHead(Rig):
     """``map = w2 . relu(bias + w_coord . coord + sum_v warp_v(upsample(z_v)))`` for one camera rig.
 
     ``proj_mats``: the reference's per-camera 3x3 ``proj_mats`` (upsampled-image pixels -> grid pixels);
@@ -174,41 +141,15 @@ class ProjectSumHead:
     Holds the normalised matrices (computed as ``ProjectFuse`` computes them), and per device and backbone
     size the geometry-only frustum boxes and, lazily, the adjoint plans."""
 
-    def __init__(self, proj_mats, upsample_shape, reducedgrid_shape):
-        if isinstance(proj_mats, torch.Tensor) or not hasattr(proj_mats, "__len__"):
-            raise TypeError(f"proj_mats must be a sequence of 3x3 matrices, got {type(proj_mats).__name__}")
-        if not 0 < len(proj_mats) <= MAX_VIEWS:
-            raise ValueError(f"1 .. {MAX_VIEWS} views, got {len(proj_mats)}")
-        try:
-            self.up_hw = tuple(int(s) for s in upsample_shape)
-            self.grid_hw = tuple(int(s) for s in reducedgrid_shape)
-        except (TypeError, ValueError):
-            raise TypeError("upsample_shape and reducedgrid_shape must be (rows, columns)") from None
-        if len(self.up_hw) != 2 or len(self.grid_hw) != 2 or min(self.up_hw + self.grid_hw) <= 0:
-            raise ValueError(f"sizes must be two positive integers, got {upsample_shape!r} and {reducedgrid_shape!r}")
-        mats = [torch.as_tensor(M) for M in proj_mats]
-        for i, M in enumerate(mats):
-            if tuple(M.shape) != (3, 3):
-                raise ValueError(f"proj_mats[{i}] must be 3x3, got {tuple(M.shape)}")
-        # the fp32 matrix kornia hands to transform_points, from the fp32-cast projection matrix (:67-68)
-        self.m_norm_cpu = torch.stack([
-            kornia_src_norm_from_dst_norm(M.float().reshape(1, 3, 3), self.up_hw, self.grid_hw)[0] for M in mats])
-        self.num_views = len(mats)
-        self._boxes, self._plans = {}, {}
-
     def boxes(self, device, backbone_hw):
-        key = (torch.device(device), tuple(backbone_hw))
-        if key not in self._boxes:
-            self._boxes[key] = ops.warp_wino_boxes(self.m_norm_cpu, self.up_hw, self.grid_hw, key[0],
-                                                   backbone_hw=key[1])
-        return self._boxes[key]
+        dev, hw = torch.device(device), tuple(backbone_hw)
+        return self.cached(("boxes", dev, hw), lambda: ops.warp_wino_boxes(self.m_norm_cpu, self.up_hw, self.grid_hw,
+                                                                           dev, backbone_hw=hw))
 
     def plans(self, device, backbone_hw):
-        key = (torch.device(device), tuple(backbone_hw))
-        if key not in self._plans:
-            self._plans[key] = [ops.WarpAdjointPlan(m, self.up_hw, self.grid_hw, key[0], backbone_hw=key[1])
-                                for m in self.m_norm_cpu]
-        return self._plans[key]
+        dev, hw = torch.device(device), tuple(backbone_hw)
+        return self.cached(("plans", dev, hw), lambda: [ops.WarpAdjointPlan(m, self.up_hw, self.grid_hw, dev,
+                                                                            backbone_hw=hw) for m in self.m_norm_cpu])
 
     def __call__(self, zs, bias, w_coord, w2, return_hidden: bool = False):
         """``zs``: one fp32 ``[B,Cm,h,w]`` tensor per view on one GPU (Cm <= 512, h <= H, w <= W; a ``z`` whose

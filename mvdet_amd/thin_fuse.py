@@ -19,7 +19,6 @@ reference's direct conv makes it).  Non-finite *planes or weights* are outside i
 """
 from __future__ import annotations
 
-import ctypes
 from types import SimpleNamespace
 
 import torch
@@ -28,37 +27,14 @@ from . import _native, ops
 from . import autograd as native_autograd
 from .ops import _stream
 from .pipeline import ProjectFuse, Workspace, band_rows
-
-MAX_VIEWS = 16  # kWarpMaxViews (csrc/warp_common.h)
+from .rig import MAX_VIEWS, Rig, check_views  # noqa: F401  (MAX_VIEWS: this module's public limit)
 
 
 def _check(n_views, src_hw, planes, w1, b1, w2, b2, w3):
-    if isinstance(planes, torch.Tensor) or not hasattr(planes, "__len__"):
-        raise TypeError(f"planes must be a sequence of tensors, got {type(planes).__name__}")
-    if not 0 < len(planes) <= MAX_VIEWS:
-        raise ValueError(f"1 .. {MAX_VIEWS} views per call, got {len(planes)}")
-    if len(planes) != n_views:
-        raise ValueError(f"{len(planes)} views for a head built for {n_views}")
-    named = [(f"planes[{i}]", p) for i, p in enumerate(planes)] + [("w1", w1), ("w2", w2), ("w3", w3)]
-    named += [(k, t) for k, t in (("b1", b1), ("b2", b2)) if t is not None]
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    params = [("w1", w1), ("w2", w2), ("w3", w3)] + [(k, t) for k, t in (("b1", b1), ("b2", b2)) if t is not None]
+    check_views("planes", planes, "the thin fused conv1", n_views, params,
+                lambda p: None if p.dim() == 4 and p.shape[1] == 1 else f"[B,1,H,W], got {tuple(p.shape)}")
     p0 = planes[0]
-    for i, p in enumerate(planes):
-        if p.dim() != 4 or p.shape[1] != 1:
-            raise ValueError(f"planes[{i}] must be [B,1,H,W], got {tuple(p.shape)}")
-        if p.shape != p0.shape:
-            raise ValueError(f"planes[{i}] {tuple(p.shape)} differs from planes[0] {tuple(p0.shape)}")
-    for name, t in named:
-        if not t.is_cuda:
-            raise ValueError(f"{name} is on {t.device}: the thin fused conv1 runs on a ROCm GPU only (no CPU fallback)")
-        if t.device != p0.device:
-            raise ValueError(f"{name} is on {t.device}, planes[0] on {p0.device}")
-    if min(p0.shape) == 0:
-        raise ValueError(f"empty planes[0] {tuple(p0.shape)}")
     if tuple(p0.shape[2:]) != tuple(src_hw):
         raise ValueError(f"planes are {tuple(p0.shape[2:])}, the head was built for {tuple(src_hw)}")
     mid = w1.shape[0] if w1.dim() == 4 else -1
@@ -87,12 +63,7 @@ def thin_conv1_forward(planes, m_norms, grid_hw, w1, b1, y1: torch.Tensor, xw=No
     Ho, Wo = int(grid_hw[0]), int(grid_hw[1])
     cout = w1.shape[0]
     layout = ops._out_layout(y1, B, cout, Ho, Wo)
-    arr = (_native.WarpView * n)()
-    for i, p in enumerate(planes):
-        st = list(p.stride())
-        st[3] = 1  # (a single column: any stride torch reports)
-        arr[i].src, arr[i].src_strides = p.data_ptr(), (ctypes.c_int64 * 4)(*st)
-        arr[i].m = (ctypes.c_float * 9)(*torch.as_tensor(m_norms[i], dtype=torch.float32).reshape(9).tolist())
+    arr = ops._view_table(planes, m_norms, unit_dim=3)  # (a single column: any stride torch reports)
     if not w1.is_contiguous() or (b1 is not None and not b1.is_contiguous()):
         raise ValueError("w1 and b1 must be contiguous")
     if xw is not None and (tuple(xw.shape) != (B, n, Ho, Wo) or xw.dtype != torch.float32 or not xw.is_contiguous()):
@@ -118,9 +89,7 @@ def thin_conv1_backward(dpre: torch.Tensor, w1: torch.Tensor, xw, n_views: int, 
     if dw is not None:
         if tuple(dw.shape) != (cout, n_views + 2, 3, 3) or dw.dtype != torch.float32 or not dw.is_contiguous():
             raise ValueError(f"dw must be a contiguous fp32 {(cout, n_views + 2, 3, 3)} tensor")
-        blocks = int(lib.mvbev_thin_conv1_backward_blocks(B, Ho, Wo))
-        if blocks <= 0:
-            raise _native.NativeError("mvbev_thin_conv1_backward_blocks: the grid does not fit one launch")
+        blocks = _native.backward_blocks("mvbev_thin_conv1_backward_blocks", B, Ho, Wo)
         partials = torch.empty(blocks * cout * n_views * 9, dtype=torch.float32, device=dev)
     if dxw is None and partials is None:
         return None
@@ -209,7 +178,7 @@ class ThinFuseFunction(torch.autograd.Function):
         return (None, dw1, db1, dw2, db2, dw3, *grads)
 
 
-class ProjectThinFuse:
+class ProjectThinFuse(Rig):
     """``map_classifier`` of ``ResProjVariant`` over the warped foot planes, for one camera rig.
 
     ``proj_mats``: the reference's per-camera 3x3 ``proj_mats`` (image-result pixels -> grid pixels);
@@ -218,33 +187,16 @@ class ProjectThinFuse:
     conv2 / conv3 methods and workspaces run after the thin kernel, and per device the adjoint plans."""
 
     def __init__(self, proj_mats, upsample_shape, reducedgrid_shape, mid_channels: int = 512):
-        if isinstance(proj_mats, torch.Tensor) or not hasattr(proj_mats, "__len__"):
-            raise TypeError(f"proj_mats must be a sequence of 3x3 matrices, got {type(proj_mats).__name__}")
-        if not 0 < len(proj_mats) <= MAX_VIEWS:
-            raise ValueError(f"1 .. {MAX_VIEWS} views, got {len(proj_mats)}")
-        try:
-            self.up_hw = tuple(int(s) for s in upsample_shape)
-            self.grid_hw = tuple(int(s) for s in reducedgrid_shape)
-        except (TypeError, ValueError):
-            raise TypeError("upsample_shape and reducedgrid_shape must be (rows, columns)") from None
-        if len(self.up_hw) != 2 or len(self.grid_hw) != 2 or min(self.up_hw + self.grid_hw) <= 0:
-            raise ValueError(f"sizes must be two positive integers, got {upsample_shape!r} and {reducedgrid_shape!r}")
-        mats = [torch.as_tensor(M) for M in proj_mats]
-        for i, M in enumerate(mats):
-            if tuple(M.shape) != (3, 3):
-                raise ValueError(f"proj_mats[{i}] must be 3x3, got {tuple(M.shape)}")
+        super().__init__(proj_mats, upsample_shape, reducedgrid_shape)
         # conv2 / conv3, their workspaces and the direct-vs-Winograd rules are the engine's; its slab (one padded
         # 8-channel slot per view) is allocated with the workspace and never warped
-        self.engine = ProjectFuse(mats, self.up_hw, self.grid_hw, 1, mid_channels=mid_channels)
-        self.m_norm_cpu = self.engine.m_norm_cpu
-        self.num_views = len(mats)
-        self._plans = {}
+        self.engine = ProjectFuse(self.mats, self.up_hw, self.grid_hw, 1, mid_channels=mid_channels)
+        self.m_norm_cpu = self.engine.m_norm_cpu  # (the engine's tensor: the same values, one object)
 
     def plans(self, device):
-        key = torch.device(device)
-        if key not in self._plans:
-            self._plans[key] = [ops.WarpAdjointPlan(m, self.up_hw, self.grid_hw, key) for m in self.m_norm_cpu]
-        return self._plans[key]
+        dev = torch.device(device)
+        return self.cached(("plans", dev), lambda: [ops.WarpAdjointPlan(m, self.up_hw, self.grid_hw, dev)
+                                                    for m in self.m_norm_cpu])
 
     def __call__(self, planes, w1, b1, w2, b2, w3) -> torch.Tensor:
         """``planes``: one fp32 ``[B,1,H,W]`` tensor per view on one GPU (any batch / channel stride: a channel

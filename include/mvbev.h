@@ -65,7 +65,7 @@ extern "C" {
 
 const char* mvbev_status_string(int status);
 /* Library / ABI version, e.g. 10000 for 1.0.0. */
-int mvbev_version(void);  /* 12400: row-Winograd F(4,3) (mvbev_pack_conv3x3_weight_wino43, mvbev_wino43_rows_split_bf16, mvbev_conv3x3_wino43_bf16x3, mvbev_conv3x3_wino43_bf16x3_cout1_partials); 12300: mvbev_coord_term_f32 (conv1's coord term as one VALU pass); 12200: the training forward's non-finite guard (mvbev_store_gated_f32, mvbev_pack_conv3x3_weight_f32_gated, mvbev_wino_rows_split_bf16_gated), per-geometry staging boxes of the fused warps (mvbev_warp_wino_boxes, mvbev_warp_views_wino_rows_ex, mvbev_warp_upsampled_wino_boxes, mvbev_warp_views_upsampled_wino_rows_ex); 12100: MVBEV_LAYOUT_SPLIT_BF16_PIX (conv data gradients' output, the warp adjoint's input); 12000: conv1's and conv2's weight gradients from the forward's row-Winograd transforms (mvbev_wino_dy_rows_f32, mvbev_conv3x3_wgrad_wino_bf16x3); 11900: row windows (mvbev_warp_views_split_bf16_rows with the non-finite report, mvbev_warp_views_exact_rows with fp16 sources), mvbev_conv3x3_f32_ex (row-band output), mvbev_bias_relu_nonfinite_f32, mvbev_zero_gated — the non-finite guard of the multi-GPU modes and the banded exact path; 11800: mvbev_conv3x3_wino_bf16x3_dgrad (row-Winograd data gradient, output-side mask); 11700: channels-last sources for the fused warps (mvbev_warp_views_wino_rows, mvbev_warp_views_upsampled_wino_rows), mvbev_nchw_to_nhwc_f32; 11600: the non-finite-feature guard (mvbev_warp_views_exact_f32; the fused warps' nonfinite report; gate arguments of mvbev_conv3x3_f32 / mvbev_conv3x3_cout1_f32; mvbev_bev_plan.guard); 11500: row-Winograd conv2 -> conv3 partials (mvbev_wino_rows_split_bf16_dil, mvbev_conv3x3_wino_bf16x3_dil, mvbev_conv3x3_wino_bf16x3_cout1_partials); 11400: mvbev_warp_nonfinite_views (non-finite geometry routes to the direct conv1); the NMS candidate order replays torch's CPU sort (ties included), mvbev_point_nms (no workspace) retired; mvbev_conv3x3_bf16x3_sched / _sched3 retired (forward schedules measured slower); 11300: row-Winograd conv1 (mvbev_pack_conv3x3_weight_wino, mvbev_wino_rows_split_bf16, mvbev_conv3x3_wino_bf16x3); 11200: mvbev_conv3x3_bf16x3_sched3 (schedules over the edge-strip tiles); 11100: edge-strip conv tiles (mvbev_conv_ring_tile_space, mvbev_conv3x3_bf16x3_ex3); 11000: ring-kernel schedules (mvbev_conv_schedule, mvbev_conv3x3_bf16x3_sched, mvbev_conv3x3_dgrad_bf16x3_sched); 10900: mvbev_conv3x3_wgrad_bf16x3_ex2 (pre-split dy rows), mvbev_split_rows_bf16; 10800: mvbev_warp_upsampled_adjoint_plan (training from backbone features), mvbev_conv3x3_cout1_backward_ex; 10700: training on split-bf16 y1 (mvbev_relu_backward_split_f32, mvbev_conv3x3_dgrad_bf16x3_ex); 10600: conv2 -> conv3 fused (mvbev_conv3x3_bf16x3_cout1_partials, mvbev_cout1_reduce_partials); 10500: mvbev_point_nms_ws (any K); 10400: MVBEV_WARP_DST_ZEROED warps; 10300: LDS-DMA ring conv (12-row tiles for split-bf16 input); 10200: native backward (10100: frustum masks, split-K tail, fused upsample+warp) */
+int mvbev_version(void);  /* 12500: mvbev_bev_plan grew by params_nonfinite (rebuild callers); non-finite parameters raise the non-finite guard (mvbev_params_nonfinite_f32, mvbev_flag_raise, mvbev_bev_plan.params_nonfinite, mvbev_thin_conv1_forward_f32_ex, mvbev_thin_conv1_weight_mask), the exact path's map through :82's same-size interpolate (mvbev_conv3x3_cout1_f32_ex), the raise folded into the partials' reduce (mvbev_cout1_reduce_partials_ex), the training backward's gated direct data gradient (mvbev_pack_conv3x3_dgrad_bf16x3_gated, mvbev_mask_gated_u32), the parameter scan riding on the per-step pack and coord term (mvbev_pack_conv3x3_weight_wino_ex, mvbev_coord_term_f32_ex); 12400: row-Winograd F(4,3) (mvbev_pack_conv3x3_weight_wino43, mvbev_wino43_rows_split_bf16, mvbev_conv3x3_wino43_bf16x3, mvbev_conv3x3_wino43_bf16x3_cout1_partials); 12300: mvbev_coord_term_f32 (conv1's coord term as one VALU pass); 12200: the training forward's non-finite guard (mvbev_store_gated_f32, mvbev_pack_conv3x3_weight_f32_gated, mvbev_wino_rows_split_bf16_gated), per-geometry staging boxes of the fused warps (mvbev_warp_wino_boxes, mvbev_warp_views_wino_rows_ex, mvbev_warp_upsampled_wino_boxes, mvbev_warp_views_upsampled_wino_rows_ex); 12100: MVBEV_LAYOUT_SPLIT_BF16_PIX (conv data gradients' output, the warp adjoint's input); 12000: conv1's and conv2's weight gradients from the forward's row-Winograd transforms (mvbev_wino_dy_rows_f32, mvbev_conv3x3_wgrad_wino_bf16x3); 11900: row windows (mvbev_warp_views_split_bf16_rows with the non-finite report, mvbev_warp_views_exact_rows with fp16 sources), mvbev_conv3x3_f32_ex (row-band output), mvbev_bias_relu_nonfinite_f32, mvbev_zero_gated — the non-finite guard of the multi-GPU modes and the banded exact path; 11800: mvbev_conv3x3_wino_bf16x3_dgrad (row-Winograd data gradient, output-side mask); 11700: channels-last sources for the fused warps (mvbev_warp_views_wino_rows, mvbev_warp_views_upsampled_wino_rows), mvbev_nchw_to_nhwc_f32; 11600: the non-finite-feature guard (mvbev_warp_views_exact_f32; the fused warps' nonfinite report; gate arguments of mvbev_conv3x3_f32 / mvbev_conv3x3_cout1_f32; mvbev_bev_plan.guard); 11500: row-Winograd conv2 -> conv3 partials (mvbev_wino_rows_split_bf16_dil, mvbev_conv3x3_wino_bf16x3_dil, mvbev_conv3x3_wino_bf16x3_cout1_partials); 11400: mvbev_warp_nonfinite_views (non-finite geometry routes to the direct conv1); the NMS candidate order replays torch's CPU sort (ties included), mvbev_point_nms (no workspace) retired; mvbev_conv3x3_bf16x3_sched / _sched3 retired (forward schedules measured slower); 11300: row-Winograd conv1 (mvbev_pack_conv3x3_weight_wino, mvbev_wino_rows_split_bf16, mvbev_conv3x3_wino_bf16x3); 11200: mvbev_conv3x3_bf16x3_sched3 (schedules over the edge-strip tiles); 11100: edge-strip conv tiles (mvbev_conv_ring_tile_space, mvbev_conv3x3_bf16x3_ex3); 11000: ring-kernel schedules (mvbev_conv_schedule, mvbev_conv3x3_bf16x3_sched, mvbev_conv3x3_dgrad_bf16x3_sched); 10900: mvbev_conv3x3_wgrad_bf16x3_ex2 (pre-split dy rows), mvbev_split_rows_bf16; 10800: mvbev_warp_upsampled_adjoint_plan (training from backbone features), mvbev_conv3x3_cout1_backward_ex; 10700: training on split-bf16 y1 (mvbev_relu_backward_split_f32, mvbev_conv3x3_dgrad_bf16x3_ex); 10600: conv2 -> conv3 fused (mvbev_conv3x3_bf16x3_cout1_partials, mvbev_cout1_reduce_partials); 10500: mvbev_point_nms_ws (any K); 10400: MVBEV_WARP_DST_ZEROED warps; 10300: LDS-DMA ring conv (12-row tiles for split-bf16 input); 10200: native backward (10100: frustum masks, split-K tail, fused upsample+warp) */
 
 /* Bilinear homography warp, zero padding, align_corners=True (kornia 0.6.11).
  *   src    : [B][C][H][W] fp32, element strides src_strides[4] (any, >= 0)
@@ -248,6 +248,26 @@ int mvbev_bias_relu_nonfinite_f32(float* y, const float* init, int64_t B, int64_
  * accumulators' initial value. */
 int mvbev_coord_term_f32(const float* w1, int64_t cin, int64_t coord_c0, const float* bias, int64_t Cout, int64_t H,
                          int64_t W, float* out, void* stream);
+/* The same with the parameters' non-finite scan riding on it (ABI 12500; nf_word NULL: as above): nf_tag is stored
+ * into the device int32 *nf_word when a value of the term is non-finite (a NaN / inf coord weight or bias, or an
+ * overflow) or when one of the two small fp32 arrays extra0 [n0], extra1 [n1] (conv2's bias, conv3's weight; may
+ * be NULL / 0) holds a NaN / inf — in training, where the weights change every step, the scan costs no launch. */
+int mvbev_coord_term_f32_ex(const float* w1, int64_t cin, int64_t coord_c0, const float* bias, int64_t Cout,
+                            int64_t H, int64_t W, float* out, int32_t* nf_word, int32_t nf_tag, const float* extra0,
+                            int64_t n0, const float* extra1, int64_t n1, void* stream);
+/* Non-finite PARAMETERS (ABI 12500; map_classifier's weights after a diverging optimizer.step(),
+ * persp_trans_detector.py:51-54 under trainer.py:47-48).  The fast path cannot keep the reference's NaN / inf
+ * pattern under them: its frustum mask never multiplies a masked view's w1 columns (the reference computes
+ * 0 * NaN = NaN), the hi/lo bf16 split of +-inf is (inf, NaN) and the Winograd weight transform G w takes
+ * differences of weights (inf - inf = NaN), where the reference keeps x * -inf = -inf, which ReLU turns into 0.
+ * mvbev_params_nonfinite_f32: params / counts are HOST arrays of nparams (1 .. 8) device fp32 arrays and their
+ * lengths; tag is stored into the device int32 *word when any value is NaN / inf (a fresh tag per weight
+ * version: no reset, no host sync) — once per weight version, beside the packs and the coord term.
+ * mvbev_flag_raise: *flag = flag_tag when *word == word_tag (one thread, in stream order) — arms a frame's
+ * non-finite guard (the gate of the exact path below) from that word. */
+int mvbev_params_nonfinite_f32(const float* const* params, const int64_t* counts, int nparams, int32_t* word,
+                               int32_t tag, void* stream);
+int mvbev_flag_raise(const int32_t* word, int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream);
 /* gate (this entry point, mvbev_conv3x3_cout1_f32, mvbev_warp_views_exact_f32; ABI 11600): a device
  * int32; when non-NULL the launch does its work only if *gate == gate_tag at the time it runs (every
  * workgroup exits at once otherwise) — a decision taken on the device in stream order, so a caller
@@ -417,6 +437,11 @@ int mvbev_nchw_to_nhwc_f32(const mvbev_warp_view* views, int nviews, int64_t B, 
 size_t mvbev_conv3x3_packed_bytes_wino(int64_t Cout, int64_t K);
 int mvbev_pack_conv3x3_weight_wino(const float* w, int64_t Cout, int64_t Cin_w, const int32_t* chan_map,
                                    int64_t K, void* w_packed, void* stream);
+/* The same with the parameters' non-finite scan riding on it (ABI 12500; nf_word NULL: as above): nf_tag is
+ * stored into the device int32 *nf_word when a weight the pack reads (every tap of every mapped input channel)
+ * is NaN / inf. */
+int mvbev_pack_conv3x3_weight_wino_ex(const float* w, int64_t Cout, int64_t Cin_w, const int32_t* chan_map,
+                                      int64_t K, void* w_packed, int32_t* nf_word, int32_t nf_tag, void* stream);
 size_t mvbev_wino_rows_bytes(const mvbev_conv_desc* desc);
 int mvbev_wino_rows_split_bf16(const void* x, const mvbev_conv_desc* desc, const uint32_t* group_mask, void* t,
                                size_t t_bytes, void* stream);
@@ -503,6 +528,12 @@ int mvbev_conv3x3_bf16x3_cout1_partials(const void* x, const mvbev_conv_desc* de
                                         void* partials, size_t partials_bytes, void* stream);
 int mvbev_cout1_reduce_partials(const void* partials, const mvbev_conv_desc* desc, int64_t Cout, int dilation3,
                                 float* map, int64_t map_row0, int64_t map_rows, void* stream);
+/* The same with mvbev_flag_raise folded in (ABI 12500; word NULL: as above): *flag = flag_tag when *word ==
+ * word_tag, stored by the launch's first thread — inference's per-frame raise of the non-finite guard from the
+ * parameters' word costs no launch of its own (the gated exact path is enqueued behind this kernel). */
+int mvbev_cout1_reduce_partials_ex(const void* partials, const mvbev_conv_desc* desc, int64_t Cout, int dilation3,
+                                   float* map, int64_t map_row0, int64_t map_rows, const int32_t* word,
+                                   int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream);
 
 /* y[b][0][r][:] = conv3x3(x[b], w, dilation=d, padding=d)[out_row0 + r], one output channel,
  * no bias.  x : [B][C][in_rows][W] holding global rows [in_row0, in_row0+in_rows) of an
@@ -511,6 +542,17 @@ int mvbev_conv3x3_cout1_f32(const float* x, int64_t B, int64_t C, int64_t H, int
                             int64_t in_row0, int64_t in_rows, int64_t out_row0, int64_t out_rows,
                             const float* w, int dilation, float* y, const int32_t* gate, int32_t gate_tag,
                             void* stream);
+/* The same with flags (ABI 12500).  MVBEV_COUT1_SAME_SIZE_INTERP: persp_trans_detector.py:82's F.interpolate of
+ * the map to its own size applied to every output value — the identity on finite values and NaN, but torch's
+ * lerp x + 0 * (x' - x) turns +-inf into NaN at that pixel.  The fast path elides that call (its map is finite);
+ * the non-finite guard's exact path, whose conv3 can give an inf under a non-finite w3 or y2, sets the flag so
+ * that its map keeps the reference's pattern.  Another bit: MVBEV_ERR_SHAPE.  word (NULL: none): mvbev_flag_raise
+ * folded in, as in mvbev_cout1_reduce_partials_ex — the training forward's conv3 arms the step's guard. */
+#define MVBEV_COUT1_SAME_SIZE_INTERP 1
+int mvbev_conv3x3_cout1_f32_ex(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, int64_t in_row0,
+                               int64_t in_rows, int64_t out_row0, int64_t out_rows, const float* w, int dilation,
+                               float* y, int flags, const int32_t* gate, int32_t gate_tag, const int32_t* word,
+                               int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream);
 
 /* ---- one-call project + fuse ----------------------------------------------
  * The inference hot path of PerspTransDetector.forward after the backbone
@@ -562,6 +604,8 @@ typedef struct mvbev_bev_plan {     /* host memory, caller-owned; filled by the 
   size_t workspace_bytes;           /* >= what mvbev_bev_fuse_workspace_bytes returns, 256-B aligned base */
   const float* b2;
   const float* w3;
+  int32_t params_nonfinite;         /* after prepare (ABI 12500): 1 = w1 / b1 / w2 / b2 / w3 hold a NaN / inf, so
+                                       every frame takes the guard's exact path (guard plans only) */
 } mvbev_bev_plan;
 int mvbev_bev_plan_init(const mvbev_bev_geometry* g, mvbev_bev_plan* plan);
 size_t mvbev_bev_fuse_workspace_bytes(const mvbev_bev_geometry* g);
@@ -575,7 +619,11 @@ int mvbev_bev_fuse_prepare(mvbev_bev_plan* plan, const float* w1, const float* b
  * each gated on that flag) rewrites the map with the reference's NaN / inf pattern — decided on the
  * device, no host sync; launches that exit at once when the features are finite.  ABI 11900: in
  * output-row chunks whose fp32 slab window holds at most 1 GiB (one chunk at configs 1, 2 and 4);
- * MVBEV_BEV_NO_GUARD in src_kind turns the guard and its workspace regions off. */
+ * MVBEV_BEV_NO_GUARD in src_kind turns the guard and its workspace regions off.  ABI 12500: prepare (which
+ * reads the weights and synchronises already) also looks for a NaN / inf in w1, b1, w2, b2, w3
+ * (mvbev_params_nonfinite_f32) and keeps the answer in plan->params_nonfinite; a guard plan then starts every
+ * frame with the flag set, so the exact path writes the map (no extra launch: the flag's per-frame reset stores
+ * the tag instead of 0).  b2 and w3 are read per frame: a caller that changes them in place prepares again. */
 int mvbev_bev_fuse(const mvbev_bev_plan* plan, const void* const* views, float* map, void* workspace,
                    size_t ws_bytes, void* stream);
 
@@ -667,6 +715,17 @@ int mvbev_conv3x3_dgrad_bf16x3_sched(const void* dy, int dy_layout, const mvbev_
 int mvbev_pack_conv3x3_dgrad_bf16x3(const float* w, int64_t Cout_w, int64_t Cin_w,
                                     const int32_t* chan_map, int64_t K_out, void* w_packed,
                                     void* stream);
+/* The same pack, run only when *gate == gate_tag (gate NULL: always; ABI 12500), and a gated tile
+ * mask, dst[i] = src[i] when *gate == gate_tag else 0 (n uint32 words): the training backward's non-finite
+ * guard.  conv1's row-Winograd data gradient mixes the dy1 rows under a 3-row tile before the products, so a
+ * NaN / inf of dy1 (a non-finite w2) would spread over its tile; behind it the direct data gradient
+ * (mvbev_conv3x3_dgrad_bf16x3_ex with these gated weights and the gated frustum mask as out_mask) rewrites the
+ * tiles when the forward's flag fired, and every workgroup of it leaves at once (an all-zero mask) when not. */
+int mvbev_pack_conv3x3_dgrad_bf16x3_gated(const float* w, int64_t Cout_w, int64_t Cin_w, const int32_t* chan_map,
+                                          int64_t K_out, void* w_packed, const int32_t* gate, int32_t gate_tag,
+                                          void* stream);
+int mvbev_mask_gated_u32(const uint32_t* src, int64_t n, uint32_t* dst, const int32_t* gate, int32_t gate_tag,
+                         void* stream);
 
 /* The data-gradient conv itself: mvbev_conv3x3_bf16x3_ex over dy (fp32, desc as for a forward
  * conv over [B][Cout_w][H][W]) with the dgrad packing, no bias / ReLU, dx in dx_layout
@@ -915,8 +974,10 @@ int mvbev_img_head_grad_weight_f32(const float* partials, int64_t nblocks, int64
  * window of mvbev_warp_views_upsampled, the one mvbev_warp_upsampled_adjoint_plan transposes; the
  * coord values are those of mvbev_fill_coord_map_f32.  A pixel whose sample coordinates are not
  * finite for some view is NaN; a pixel outside a view's source gets exactly 0 from that view (its
- * data is not read).  NaN / Inf in z or the parameters are outside the contract: the commuted order
- * cannot reproduce where the reference's 0 * NaN lands.
+ * data is not read).  NaN / Inf in z are outside the contract: the commuted order cannot reproduce
+ * where the reference's 0 * NaN lands.  NaN / Inf in bias, w_coord and w2 with finite z are inside it
+ * (ABI 12500): every product is formed, and an infinite map value is stored as NaN, as :81's
+ * F.interpolate of the map to its own size makes it (the identity otherwise).
  * Range: 1 <= nviews <= 16, 1 <= Cm <= 512 (any, not only multiples of 4), H >= h, W >= w (else
  * MVBEV_ERR_SHAPE; a size <= 0 is MVBEV_ERR_RANK, a channel stride != 1 or a negative stride
  * MVBEV_ERR_STRIDE, a missing pointer MVBEV_ERR_NULL). */
@@ -963,14 +1024,24 @@ int mvbev_warp_sum_head_grad_params_f32(const float* partials, int64_t nblocks, 
  * b1 [Cout] or NULL.  y1 contiguous in y1_layout: MVBEV_LAYOUT_F32 ([B][Cout][Ho][Wo]) or
  * MVBEV_LAYOUT_SPLIT_BF16 ([B][Cout / 8][Ho][Wo] pieces of bf16 hi[8], lo[8], 16-B aligned: the input of
  * mvbev_wino_rows_split_bf16_dil and the ring conv).  xw (NULL in inference): the N warped planes,
- * [B][N][Ho][Wo] fp32 contiguous, which the backward reads.  NaN / Inf in the planes or the weights are outside
- * the contract (a view skipped over a tile does not multiply them).
+ * [B][N][Ho][Wo] fp32 contiguous, which the backward reads.  NaN / Inf in the planes are outside the contract
+ * (a view skipped over a tile does not multiply them).  NaN / Inf in the weights (ABI 12500) are inside it
+ * through mvbev_thin_conv1_forward_f32_ex: w_mask (NULL: as this entry point) is a device int32 whose bit v says
+ * that view v's columns w1[:, v] hold a non-finite value (mvbev_thin_conv1_weight_mask, once per weight
+ * version); such a view is evaluated over every tile, so its zero samples meet the weight (0 * NaN = NaN, the
+ * reference's pixels).  With finite weights the word is 0 and y1 is bitwise this entry point's.
  * Range: 1 <= nviews <= 16, Cout % 8 == 0, every tensor below 2^31 elements (else MVBEV_ERR_SHAPE, as an
  * unknown layout; a size <= 0 is MVBEV_ERR_RANK, a column stride != 1 or a negative stride MVBEV_ERR_STRIDE, a
  * missing pointer MVBEV_ERR_NULL, a misaligned split y1 MVBEV_ERR_ALIGN). */
 int mvbev_thin_conv1_forward_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t H, int64_t W, int64_t Ho,
                                  int64_t Wo, const float* w1, const float* b1, int64_t Cout, void* y1, int y1_layout,
                                  float* xw, void* stream);
+int mvbev_thin_conv1_forward_f32_ex(const mvbev_warp_view* views, int nviews, int64_t B, int64_t H, int64_t W,
+                                    int64_t Ho, int64_t Wo, const float* w1, const float* b1, int64_t Cout, void* y1,
+                                    int y1_layout, float* xw, const int32_t* w_mask, void* stream);
+/* *mask (device int32) = bit v set when w1[:, v] (v < nviews of the [Cout][nviews + 2][3][3] weight) holds a
+ * NaN / inf; one workgroup, every launch writes the whole word (no reset needed). */
+int mvbev_thin_conv1_weight_mask(const float* w1, int nviews, int64_t Cout, int32_t* mask, void* stream);
 
 /* Workgroups of mvbev_thin_conv1_backward_f32's weight-gradient pass = the leading extent of its partials:
  * B * ceil(Ho / 8) * ceil(Wo / 32) (0: invalid sizes). */

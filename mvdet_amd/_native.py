@@ -121,10 +121,22 @@ EXPORTS = (
     "mvbev_thin_conv1_backward_blocks",
     "mvbev_thin_conv1_backward_f32",
     "mvbev_thin_conv1_grad_weight_f32",
+    # non-finite parameters raise the non-finite guard (ABI 12500)
+    "mvbev_params_nonfinite_f32",
+    "mvbev_flag_raise",
+    "mvbev_thin_conv1_forward_f32_ex",
+    "mvbev_thin_conv1_weight_mask",
+    "mvbev_conv3x3_cout1_f32_ex",
+    "mvbev_cout1_reduce_partials_ex",
+    "mvbev_pack_conv3x3_dgrad_bf16x3_gated",
+    "mvbev_mask_gated_u32",
+    "mvbev_pack_conv3x3_weight_wino_ex",
+    "mvbev_coord_term_f32_ex",
 )
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
 BEV_SRC_CHANNELS_LAST = 16  # MVBEV_BEV_SRC_CHANNELS_LAST (flag)
 BEV_NO_GUARD = 32  # MVBEV_BEV_NO_GUARD (flag, ABI 11900)
+COUT1_SAME_SIZE_INTERP = 1  # MVBEV_COUT1_SAME_SIZE_INTERP (mvbev_conv3x3_cout1_f32_ex, ABI 12500)
 WARP_DST_ZEROED = 1  # MVBEV_WARP_DST_ZEROED
 WARP_SRC_F16 = 2  # MVBEV_WARP_SRC_F16 (mvbev_warp_views_wino_rows, ABI 11900)
 WARP_WINO43 = 4  # MVBEV_WARP_WINO43 (the fused warps write the F(4,3) transform, ABI 12400)
@@ -183,7 +195,7 @@ class BevPlan(ctypes.Structure):
                 ("prepared", ctypes.c_int32), ("wino2", ctypes.c_int32), ("guard", ctypes.c_int32),
                 ("Cs", ctypes.c_int64), ("tiles", ctypes.c_int64), ("off", ctypes.c_size_t * 24),
                 ("workspace_bytes", ctypes.c_size_t),
-                ("b2", ctypes.c_void_p), ("w3", ctypes.c_void_p)]
+                ("b2", ctypes.c_void_p), ("w3", ctypes.c_void_p), ("params_nonfinite", ctypes.c_int32)]
 
 
 class LossItem(ctypes.Structure):
@@ -368,6 +380,15 @@ def _declare(lib):
                                                   _i64, _i64, _p]
     lib.mvbev_pack_conv3x3_dgrad_bf16x3.restype = ctypes.c_int
     lib.mvbev_pack_conv3x3_dgrad_bf16x3.argtypes = [_p, _i64, _i64, _p, _i64, _p, _p]
+    lib.mvbev_pack_conv3x3_dgrad_bf16x3_gated.restype = ctypes.c_int
+    lib.mvbev_pack_conv3x3_dgrad_bf16x3_gated.argtypes = [_p, _i64, _i64, _p, _i64, _p, _p, ctypes.c_int32, _p]
+    lib.mvbev_pack_conv3x3_weight_wino_ex.restype = ctypes.c_int
+    lib.mvbev_pack_conv3x3_weight_wino_ex.argtypes = [_p, _i64, _i64, _p, _i64, _p, _p, ctypes.c_int32, _p]
+    lib.mvbev_coord_term_f32_ex.restype = ctypes.c_int
+    lib.mvbev_coord_term_f32_ex.argtypes = [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, ctypes.c_int32, _p, _i64,
+                                            _p, _i64, _p]
+    lib.mvbev_mask_gated_u32.restype = ctypes.c_int
+    lib.mvbev_mask_gated_u32.argtypes = [_p, _i64, _p, _p, ctypes.c_int32, _p]
     lib.mvbev_conv3x3_wgrad_workspace_bytes.restype = ctypes.c_size_t
     lib.mvbev_conv3x3_wgrad_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), _i64]
     lib.mvbev_conv3x3_bias_coord_grad_f32.restype = ctypes.c_int
@@ -407,6 +428,10 @@ def _declare(lib):
     lib.mvbev_conv3x3_cout1_f32.restype = ctypes.c_int
     lib.mvbev_conv3x3_cout1_f32.argtypes = [_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p,
                                             ctypes.c_int, _p, _p, ctypes.c_int32, _p]
+    lib.mvbev_conv3x3_cout1_f32_ex.restype = ctypes.c_int
+    lib.mvbev_conv3x3_cout1_f32_ex.argtypes = [_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p,
+                                               ctypes.c_int, _p, ctypes.c_int, _p, ctypes.c_int32, _p, ctypes.c_int32,
+                                               _p, ctypes.c_int32, _p]
     lib.mvbev_warp_views_split_bf16_ex.restype = ctypes.c_int
     lib.mvbev_warp_views_split_bf16_ex.argtypes = [ctypes.POINTER(WarpView), ctypes.c_int, ctypes.c_int, _i64, _i64,
                                                    _i64, _i64, _i64, _i64, ctypes.c_int, _p]
@@ -430,6 +455,9 @@ def _declare(lib):
     lib.mvbev_relu_backward_split_f32.argtypes = [_p, _p, _i64, _i64, _i64, _i64, _p, _p]
     lib.mvbev_cout1_reduce_partials.restype = ctypes.c_int
     lib.mvbev_cout1_reduce_partials.argtypes = [_p, ctypes.POINTER(ConvDesc), _i64, ctypes.c_int, _p, _i64, _i64, _p]
+    lib.mvbev_cout1_reduce_partials_ex.restype = ctypes.c_int
+    lib.mvbev_cout1_reduce_partials_ex.argtypes = lib.mvbev_cout1_reduce_partials.argtypes[:-1] + [
+        _p, ctypes.c_int32, _p, ctypes.c_int32, _p]
     items = ctypes.POINTER(LossItem)
     lib.mvbev_adaptive_max_pool_f32.restype = ctypes.c_int
     lib.mvbev_adaptive_max_pool_f32.argtypes = [items, ctypes.c_int, _i64, _p]
@@ -464,6 +492,15 @@ def _declare(lib):
     lib.mvbev_thin_conv1_forward_f32.restype = ctypes.c_int
     lib.mvbev_thin_conv1_forward_f32.argtypes = ([ctypes.POINTER(WarpView), ctypes.c_int] + [_i64] * 5 +
                                                  [_p, _p, _i64, _p, ctypes.c_int, _p, _p])  # w1, b1, Cout, y1, layout, xw
+    lib.mvbev_thin_conv1_forward_f32_ex.restype = ctypes.c_int
+    lib.mvbev_thin_conv1_forward_f32_ex.argtypes = lib.mvbev_thin_conv1_forward_f32.argtypes[:-1] + [_p, _p]  # w_mask
+    lib.mvbev_thin_conv1_weight_mask.restype = ctypes.c_int
+    lib.mvbev_thin_conv1_weight_mask.argtypes = [_p, ctypes.c_int, _i64, _p, _p]
+    lib.mvbev_params_nonfinite_f32.restype = ctypes.c_int
+    lib.mvbev_params_nonfinite_f32.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_i64), ctypes.c_int, _p,
+                                               ctypes.c_int32, _p]
+    lib.mvbev_flag_raise.restype = ctypes.c_int
+    lib.mvbev_flag_raise.argtypes = [_p, ctypes.c_int32, _p, ctypes.c_int32, _p]
     lib.mvbev_thin_conv1_backward_blocks.restype = _i64
     lib.mvbev_thin_conv1_backward_blocks.argtypes = [_i64] * 3
     lib.mvbev_thin_conv1_backward_f32.restype = ctypes.c_int

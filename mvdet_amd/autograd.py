@@ -110,7 +110,8 @@ def _bwd_state(engine: ProjectFuse):
     st = getattr(engine, "_bwd", None)
     if st is None:
         nc = engine.num_cam * engine.C
-        st = SimpleNamespace(dgrad1=ops.PackedDgrad3x3(nc), dgrad2=ops.PackedDgrad3x3(engine.mid), wg_ws={})
+        st = SimpleNamespace(dgrad1=ops.PackedDgrad3x3(nc), dgrad2=ops.PackedDgrad3x3(engine.mid), wg_ws={},
+                             ones_mask={}, gated_mask={})  # (the last two: _dgrad1_exact's tile masks per device)
         engine._bwd = st
     return st
 
@@ -211,6 +212,35 @@ def _dgrad1_wino(engine: ProjectFuse, st, dy1s: torch.Tensor, w1: torch.Tensor, 
     ops.wino_rows(dy1s, d, st.t1d)
     cm = engine.conv1_mask(dy1s.device, 0, H, tile_h=12)
     ops.conv3x3_wino_dgrad(st.t1d, d, st.pack1t.get(w1), nc, dslab, out_mask=cm, cot_per_group=C // ops.BN)
+
+
+def _dgrad1_exact(engine: ProjectFuse, st, ws: Workspace, dy1s: torch.Tensor, w1: torch.Tensor,
+                  dslab: torch.Tensor) -> None:
+    """The backward's share of the non-finite guard, behind ``_dgrad1_wino``: B^T mixes the five dy1 rows under a
+    3-row tile before the products, so a NaN / inf of dy1 (a non-finite w2: the forward's flag fired) would reach
+    every output row of its tile where the reference's direct sum keeps it to the 3 x 3 neighbourhood.  The
+    direct data gradient (``ops.conv3x3_dgrad``, every product formed) rewrites the same tiles of ``dslab`` —
+    gated on the forward's flag without a host sync: its weights are packed gated, and its output-side tile mask
+    is the frustum mask when the flag holds the step's tag and all zero otherwise, so with a finite step every
+    workgroup leaves at once.  The flag is the engine's per device and takes a fresh tag with every training
+    forward: a backward that runs after a LATER forward of the same engine (two losses, checkpointing) finds the
+    later step's tag and skips this rewrite — the Winograd gradient's superset pattern then stands."""
+    H = engine.grid_hw[0]
+    C = engine.C
+    dev = dy1s.device
+    gate = (ws.nf, ws.nf_tag)
+    cm = engine.conv1_mask(dev, 0, H, tile_h=ops.dgrad_tile_rows(True, 1))
+    if cm is None:  # no frustum mask: every tile of every view
+        tiles = -(-H // ops.dgrad_tile_rows(True, 1)) * -(-engine.grid_hw[1] // _native.TILE_W)
+        cm = st.ones_mask.get(str(dev))
+        if cm is None or cm.numel() != tiles:
+            cm = st.ones_mask[str(dev)] = torch.full((tiles,), -1, dtype=torch.int32, device=dev)
+    gm = st.gated_mask.get(str(dev))
+    if gm is None or gm.numel() != cm.numel():
+        gm = st.gated_mask[str(dev)] = torch.zeros_like(cm)
+    ops.mask_gated(cm, gm, gate)
+    ops.conv3x3_dgrad(dy1s, st.dgrad1.get_gated(w1.detach().contiguous(), gate), w1, 1, out=dslab, out_mask=gm,
+                      cot_per_group=C // ops.BN)
 
 
 def _wgrad_wino_fits(K: int, cout: int, H: int, W: int, B: int, dilation: int) -> bool:
@@ -408,6 +438,8 @@ class ProjectFuseFunction(torch.autograd.Function):
                                     dtype=torch.bfloat16, device=dev)
                 if dy1s is not None and _dgrad1_wino_applies(engine, cp, dev):
                     _dgrad1_wino(engine, st, dy1s, w1, dslab)
+                    if engine.nonfinite_guard and ws.t_from_warp and ws.nf is not None:
+                        _dgrad1_exact(engine, st, ws, dy1s, w1, dslab)
                 else:
                     # frustum: a view's tiles of dslab that its warp never samples are not computed
                     cm = (engine.conv1_mask(dev, 0, H, tile_h=ops.dgrad_tile_rows(dy1s is not None, 1))

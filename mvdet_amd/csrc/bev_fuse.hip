@@ -307,6 +307,26 @@ int mvbev_bev_fuse_prepare(mvbev_bev_plan* p, const float* w1, const float* b1, 
   else
     BEV_TRY(mvbev_pack_conv3x3_weight_bf16x3(w2, kMid, kMid, nullptr, kMid, at<void>(ws, p, R_PACK2), stream));
   p->guard = p->guard && p->wino;  // non-finite geometry already runs the direct convs
+  p->params_nonfinite = 0;
+  if (p->guard) {
+    // (ABI 12500) a NaN / inf in the parameters: the frustum mask, the hi/lo split and G w would not keep the
+    // reference's pattern, so every frame of this plan takes the exact path (mvbev_bev_fuse starts it with the
+    // flag set).  Decided here, where the weights are read and the stream is drained anyway.
+    const float* params[5] = {w1, w2, w3, b1, b2};
+    const int64_t counts[5] = {kMid * cin * 9, (int64_t)kMid * kMid * 9, (int64_t)kMid * 9, kMid, kMid};
+    const int np = 3 + (b1 ? 1 : 0) + (b2 ? 1 : 0);
+    if (!b1 && b2) params[3] = b2;
+    int32_t* word = at<int32_t>(ws, p, R_GFLAG);  // (free until the first frame, which resets it)
+    int32_t bad = 0;
+    if (hipMemsetAsync(word, 0, 4, s) != hipSuccess) return MVBEV_ERR_HIP;
+    BEV_TRY_SYNC(mvbev_params_nonfinite_f32(params, counts, np, word, 1, stream), s);
+    if (hipMemcpyAsync(&bad, word, 4, hipMemcpyDeviceToHost, s) != hipSuccess) {
+      (void)hipStreamSynchronize(s);
+      return MVBEV_ERR_HIP;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) return MVBEV_ERR_HIP;
+    p->params_nonfinite = bad == 1 ? 1 : 0;
+  }
   if (p->guard) {  // the exact path's fp32 packs; its slab's padding channels stay zero
     BEV_TRY(mvbev_pack_conv3x3_weight_f32(w1, kMid, cin, at<int32_t>(ws, p, R_MAP1), K, at<float>(ws, p, R_GPACK1),
                                           stream));
@@ -341,7 +361,10 @@ int mvbev_bev_fuse(const mvbev_bev_plan* p, const void* const* views, float* map
   const bool backbone = kind_of(g) == MVBEV_BEV_SRC_BACKBONE_F32;
   void* y1 = at<void>(ws, p, R_Y1);
   int32_t* gflag = p->guard ? at<int32_t>(ws, p, R_GFLAG) : nullptr;
-  if (gflag && hipMemsetAsync(gflag, 0, 4, static_cast<hipStream_t>(stream)) != hipSuccess) return MVBEV_ERR_HIP;
+  // the frame's flag: 0, or already the tag when prepare found a non-finite parameter (ABI 12500)
+  if (gflag && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gflag), p->params_nonfinite ? 1 : 0, 1,
+                                 static_cast<hipStream_t>(stream)) != hipSuccess)
+    return MVBEV_ERR_HIP;
   // a4 + a5 + a6 (+ conv1's B^T): the warp of every view in one launch
   if (p->wino) {
     t_views(p, views, big, wv);
@@ -431,8 +454,9 @@ int mvbev_bev_fuse(const mvbev_bev_plan* p, const void* const* views, float* map
       BEV_TRY(mvbev_conv3x3_f32(gy1, &e2, at<float>(ws, p, R_GPACK2), p->b2, nullptr, kMid, 2, 1, gy2, gflag, 1,
                                 stream));
       for (int64_t bi = 0; bi < g.B; ++bi)  // (a row chunk of a B > 1 map is not one contiguous block)
-        BEV_TRY(mvbev_conv3x3_cout1_f32(gy2 + bi * kMid * (b2 - a2) * g.Wo, 1, kMid, g.Ho, g.Wo, a2, b2 - a2, a, b - a,
-                                        p->w3, 4, map + (bi * g.Ho + a) * g.Wo, gflag, 1, stream));
+        BEV_TRY(mvbev_conv3x3_cout1_f32_ex(gy2 + bi * kMid * (b2 - a2) * g.Wo, 1, kMid, g.Ho, g.Wo, a2, b2 - a2, a,
+                                           b - a, p->w3, 4, map + (bi * g.Ho + a) * g.Wo,
+                                           MVBEV_COUT1_SAME_SIZE_INTERP, gflag, 1, nullptr, 0, nullptr, 0, stream));  // (:82: inf -> NaN)
     }
   }
   return MVBEV_OK;

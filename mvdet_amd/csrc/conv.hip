@@ -269,13 +269,32 @@ __global__ __launch_bounds__(64 * NWAVES, MVBEV_CONV_MINWAVES) void conv3x3_mfma
   emit(acc11, 1, 1);
 }
 
+// mvbev_flag_raise folded into a launch that runs anyway (the training forward's conv3): the launch's first thread
+// stores flag_tag into *flag when *word == word_tag (word NULL: nothing)
+struct FlagRaise {
+  const int32_t* word;
+  int32_t word_tag;
+  int32_t* flag;
+  int32_t flag_tag;
+  __device__ __forceinline__ void raise_once() const {
+    if (word && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0 && *word == word_tag) *flag = flag_tag;
+  }
+};
+
 constexpr int C1_WAVES = 8;  // waves per conv3 block: each sums C/8 channels of 64 pixels
+
+// persp_trans_detector.py:82's F.interpolate of the map to its own size (MVBEV_COUT1_SAME_SIZE_INTERP, ABI 12500):
+// the identity on finite values and NaN, but torch's lerp x + 0 * (x' - x) turns +-inf into NaN at that pixel.
+// The fast path elides the call (a finite map); the exact path, whose map can hold an inf, applies it here.
+__device__ __forceinline__ float same_size_interp(float v) { return isinf(v) ? __builtin_nanf("") : v; }
 
 template <int DIL>
 __global__ __launch_bounds__(64 * C1_WAVES) void conv3x3_cout1_kernel(
     const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, int C, int H,
-    int W, int in_row0, int in_rows, int out_row0, const int32_t* gate, int32_t gate_tag) {
+    int W, int in_row0, int in_rows, int out_row0, const int32_t* gate, int32_t gate_tag, int interp_same_size,
+    const FlagRaise fr) {
   __shared__ float part[C1_WAVES][64];
+  fr.raise_once();
   if (gate && *gate != gate_tag) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -330,7 +349,7 @@ __global__ __launch_bounds__(64 * C1_WAVES) void conv3x3_cout1_kernel(
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < C1_WAVES; ++i) sum += part[i][lane];
-    y[((int64_t)b * gridDim.y + blockIdx.y) * W + col] = sum;
+    y[((int64_t)b * gridDim.y + blockIdx.y) * W + col] = interp_same_size ? same_size_interp(sum) : sum;
   }
 }
 
@@ -347,9 +366,11 @@ constexpr int C1Q_SUBS = C1Q_WAVES * (64 / C1Q_QUADS);  // channel subsets per b
 template <int DIL>
 __global__ __launch_bounds__(64 * C1Q_WAVES) void conv3x3_cout1_q4_kernel(
     const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, int C, int H,
-    int W, int in_row0, int in_rows, int out_row0, int out_rows, const int32_t* gate, int32_t gate_tag) {
+    int W, int in_row0, int in_rows, int out_row0, int out_rows, const int32_t* gate, int32_t gate_tag, int interp_same_size,
+    const FlagRaise fr) {
   static_assert(DIL % 4 == 0, "16-B aligned taps");
   __shared__ f32x4_t part[C1Q_WAVES][C1Q_QUADS];
+  fr.raise_once();
   if (gate && *gate != gate_tag) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -409,6 +430,10 @@ __global__ __launch_bounds__(64 * C1Q_WAVES) void conv3x3_cout1_q4_kernel(
     f32x4_t sum = part[0][qi];
 #pragma unroll
     for (int i = 1; i < C1Q_WAVES; ++i) sum += part[i][qi];
+    if (interp_same_size) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sum[e] = same_size_interp(sum[e]);
+    }
     *reinterpret_cast<f32x4_t*>(y + ((int64_t)b * out_rows + r) * W + col) = sum;
   }
 }
@@ -460,8 +485,18 @@ __global__ __launch_bounds__(256) void bias_relu_nonfinite_kernel(float* __restr
 constexpr int kCtCh = 32;  // output channels per block
 __global__ __launch_bounds__(256) void coord_term_kernel(const float* __restrict__ w, int64_t w_cout_stride,
                                                          const float* __restrict__ bias, float* __restrict__ out,
-                                                         int Cout, int H, int W) {
+                                                         int Cout, int H, int W, int32_t* __restrict__ nf_word,
+                                                         int32_t nf_tag, const float* __restrict__ extra0, int n0,
+                                                         const float* __restrict__ extra1, int n1) {
   const int r = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+  // (nf_word: the parameters' non-finite scan rides on this launch — a non-finite coord weight or bias shows in
+  // the term itself, and the first block also looks through two small arrays, conv2's bias and conv3's weight)
+  bool bad = false;
+  if (nf_word && (blockIdx.x | blockIdx.y | blockIdx.z) == 0) {
+    for (int i = threadIdx.x; i < n0; i += 256) bad = bad || !isfinite(extra0[i]);
+    for (int i = threadIdx.x; i < n1; i += 256) bad = bad || !isfinite(extra1[i]);
+    if (bad) *nf_word = nf_tag;
+  }
   if (q >= W) return;
   float xv[3][3], yv[3][3];  // [ky][kx] the window's coord values, 0 where the tap is padding
 #pragma unroll
@@ -488,23 +523,86 @@ __global__ __launch_bounds__(256) void coord_term_kernel(const float* __restrict
         acc = fmaf(wc[ky * 3 + kx], xv[ky][kx], acc);
         acc = fmaf(wc[9 + ky * 3 + kx], yv[ky][kx], acc);
       }
-    o[(int64_t)c * H * W] = acc + (bias ? bias[c] : 0.f);
+    const float v = acc + (bias ? bias[c] : 0.f);
+    bad = bad || !isfinite(v);
+    o[(int64_t)c * H * W] = v;
   }
+  if (nf_word && bad) *nf_word = nf_tag;
+}
+
+// The parameters' non-finite word (ABI 12500): tag is stored into *word when any value of up to kNfMaxArrays fp32
+// arrays (map_classifier's w1, b1, w2, b2, w3) is NaN / inf — once per weight version, where the packs and the
+// coord term are rebuilt.  A fresh tag per version, so the word needs no reset (every writer stores the same
+// value).  flag_raise_kernel then arms a frame's non-finite guard from it: *flag = flag_tag when *word == word_tag,
+// one thread, no host sync — the fast path's frustum mask, hi/lo split and G w cannot keep the reference's
+// pattern under a non-finite weight, the gated exact path can.
+constexpr int kNfMaxArrays = 8;
+struct NfArrays {
+  const float* p[kNfMaxArrays];
+  int64_t n[kNfMaxArrays];
+  int count;
+};
+__global__ __launch_bounds__(256) void params_nonfinite_kernel(const NfArrays a, int32_t* __restrict__ word,
+                                                               int32_t tag) {
+  bool bad = false;
+  for (int k = 0; k < a.count; ++k) {
+    const float* __restrict__ p = a.p[k];
+    const int64_t n = a.n[k];
+    const int64_t tid = blockIdx.x * (int64_t)256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+    // 16-B loads over the aligned middle (a weight tensor is 66 MB at config 2 and is scanned every training
+    // step), scalar ones over the unaligned head and the tail
+    const int64_t mis = (4 - (int64_t)((reinterpret_cast<uintptr_t>(p) >> 2) & 3)) & 3, head = mis < n ? mis : n;
+    const int64_t n4 = (n - head) / 4;
+    const floatx4* __restrict__ p4 = reinterpret_cast<const floatx4*>(p + head);
+    for (int64_t i = tid; i < n4; i += nth) {
+      const floatx4 v = p4[i];
+      bad = bad || !isfinite(v[0]) || !isfinite(v[1]) || !isfinite(v[2]) || !isfinite(v[3]);
+    }
+    for (int64_t i = tid; i < head; i += nth) bad = bad || !isfinite(p[i]);
+    for (int64_t i = head + 4 * n4 + tid; i < n; i += nth) bad = bad || !isfinite(p[i]);
+  }
+  if (bad) *word = tag;
+}
+
+// dst[i] = src[i] when *gate == gate_tag, else 0: a tile mask that enables a launch's workgroups only when the
+// non-finite guard fired (the backward's direct data gradient behind the row-Winograd one)
+__global__ __launch_bounds__(256) void mask_gated_kernel(const uint32_t* __restrict__ src, int64_t n,
+                                                         uint32_t* __restrict__ dst, const int32_t* gate,
+                                                         int32_t gate_tag) {
+  const bool on = *gate == gate_tag;
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    dst[i] = on ? src[i] : 0u;
+}
+
+__global__ void flag_raise_kernel(const int32_t* __restrict__ word, int32_t word_tag, int32_t* __restrict__ flag,
+                                  int32_t flag_tag) {
+  if (threadIdx.x == 0 && *word == word_tag) *flag = flag_tag;
 }
 
 }  // namespace mvbev
 
 extern "C" {
 
+int mvbev_coord_term_f32_ex(const float* w1, int64_t cin, int64_t coord_c0, const float* bias, int64_t Cout,
+                            int64_t H, int64_t W, float* out, int32_t* nf_word, int32_t nf_tag, const float* extra0,
+                            int64_t n0, const float* extra1, int64_t n1, void* stream);
+
 int mvbev_coord_term_f32(const float* w1, int64_t cin, int64_t coord_c0, const float* bias, int64_t Cout, int64_t H,
                          int64_t W, float* out, void* stream) {
+  return mvbev_coord_term_f32_ex(w1, cin, coord_c0, bias, Cout, H, W, out, nullptr, 0, nullptr, 0, nullptr, 0, stream);
+}
+
+int mvbev_coord_term_f32_ex(const float* w1, int64_t cin, int64_t coord_c0, const float* bias, int64_t Cout,
+                            int64_t H, int64_t W, float* out, int32_t* nf_word, int32_t nf_tag, const float* extra0,
+                            int64_t n0, const float* extra1, int64_t n1, void* stream) {
   using namespace mvbev;
-  if (!w1 || !out) return MVBEV_ERR_NULL;
+  if (!w1 || !out || (n0 > 0 && !extra0) || (n1 > 0 && !extra1)) return MVBEV_ERR_NULL;
+  if (n0 < 0 || n1 < 0 || n0 > INT32_MAX || n1 > INT32_MAX) return MVBEV_ERR_SHAPE;
   if (cin <= 0 || Cout <= 0 || H <= 1 || W <= 1) return MVBEV_ERR_RANK;
   if (coord_c0 < 0 || coord_c0 + 2 > cin || H > 65535 || H * W > INT32_MAX - 256) return MVBEV_ERR_SHAPE;
   const dim3 grid((unsigned)ceil_div(W, (int64_t)256), (unsigned)H, (unsigned)ceil_div(Cout, (int64_t)kCtCh));
   hipLaunchKernelGGL(coord_term_kernel, grid, dim3(256), 0, as_stream(stream), w1 + coord_c0 * 9, cin * 9, bias, out,
-                     (int)Cout, (int)H, (int)W);
+                     (int)Cout, (int)H, (int)W, nf_word, nf_tag, extra0, (int)n0, extra1, (int)n1);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }
@@ -524,6 +622,46 @@ int mvbev_bias_relu_nonfinite_f32(float* y, const float* init, int64_t B, int64_
   else
     hipLaunchKernelGGL(bias_relu_nonfinite_kernel<false>, grid, dim3(256), 0, as_stream(stream), y, init, (int)C,
                        (int)rows, (int)W, (int)H, (int)row0, relu, n, flag, tag);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
+int mvbev_params_nonfinite_f32(const float* const* params, const int64_t* counts, int nparams, int32_t* word,
+                               int32_t tag, void* stream) {
+  using namespace mvbev;
+  if (!params || !counts || !word) return MVBEV_ERR_NULL;
+  if (nparams <= 0 || nparams > kNfMaxArrays) return MVBEV_ERR_SHAPE;
+  NfArrays a = {};
+  int64_t longest = 0;
+  for (int k = 0; k < nparams; ++k) {
+    if (!params[k]) return MVBEV_ERR_NULL;
+    if (counts[k] <= 0) return MVBEV_ERR_RANK;
+    a.p[k] = params[k];
+    a.n[k] = counts[k];
+    longest = std::max(longest, counts[k]);
+  }
+  a.count = nparams;
+  const dim3 grid((unsigned)std::min<int64_t>(ceil_div(longest, (int64_t)256), 2048));
+  hipLaunchKernelGGL(params_nonfinite_kernel, grid, dim3(256), 0, as_stream(stream), a, word, tag);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
+int mvbev_mask_gated_u32(const uint32_t* src, int64_t n, uint32_t* dst, const int32_t* gate, int32_t gate_tag,
+                         void* stream) {
+  using namespace mvbev;
+  if (!src || !dst || !gate) return MVBEV_ERR_NULL;
+  if (n <= 0) return MVBEV_ERR_RANK;
+  const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n, (int64_t)256), 1024));
+  hipLaunchKernelGGL(mask_gated_kernel, grid, dim3(256), 0, as_stream(stream), src, n, dst, gate, gate_tag);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
+int mvbev_flag_raise(const int32_t* word, int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream) {
+  using namespace mvbev;
+  if (!word || !flag) return MVBEV_ERR_NULL;
+  hipLaunchKernelGGL(flag_raise_kernel, dim3(1), dim3(64), 0, as_stream(stream), word, word_tag, flag, flag_tag);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }
@@ -620,11 +758,28 @@ int mvbev_conv3x3_f32_ex(const float* x, const mvbev_conv_desc* d, const float* 
   return MVBEV_OK;
 }
 
+int mvbev_conv3x3_cout1_f32_ex(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, int64_t in_row0,
+                               int64_t in_rows, int64_t out_row0, int64_t out_rows, const float* w, int dilation,
+                               float* y, int flags, const int32_t* gate, int32_t gate_tag, const int32_t* word,
+                               int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream);
+
 int mvbev_conv3x3_cout1_f32(const float* x, int64_t B, int64_t C, int64_t H, int64_t W,
                             int64_t in_row0, int64_t in_rows, int64_t out_row0, int64_t out_rows,
                             const float* w, int dilation, float* y, const int32_t* gate, int32_t gate_tag,
                             void* stream) {
+  return mvbev_conv3x3_cout1_f32_ex(x, B, C, H, W, in_row0, in_rows, out_row0, out_rows, w, dilation, y, 0, gate,
+                                    gate_tag, nullptr, 0, nullptr, 0, stream);
+}
+
+int mvbev_conv3x3_cout1_f32_ex(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, int64_t in_row0,
+                               int64_t in_rows, int64_t out_row0, int64_t out_rows, const float* w, int dilation,
+                               float* y, int flags, const int32_t* gate, int32_t gate_tag, const int32_t* word,
+                               int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream) {
   using namespace mvbev;
+  if (flags & ~MVBEV_COUT1_SAME_SIZE_INTERP) return MVBEV_ERR_SHAPE;
+  if (word && !flag) return MVBEV_ERR_NULL;
+  const FlagRaise fr{word, word_tag, flag, flag_tag};
+  const int interp = (flags & MVBEV_COUT1_SAME_SIZE_INTERP) ? 1 : 0;
   if (!x || !w || !y) return MVBEV_ERR_NULL;
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || in_rows <= 0 || out_rows <= 0)
     return MVBEV_ERR_RANK;
@@ -635,14 +790,14 @@ int mvbev_conv3x3_cout1_f32(const float* x, int64_t B, int64_t C, int64_t H, int
       (reinterpret_cast<uintptr_t>(y) & 15) == 0 && out_rows * (W / 4) <= (int64_t)INT32_MAX - 64) {
     dim3 qgrid((unsigned)ceil_div(out_rows * (W / 4), C1Q_QUADS), (unsigned)B);
     hipLaunchKernelGGL(conv3x3_cout1_q4_kernel<4>, qgrid, dim3(64 * C1Q_WAVES), 0, s, x, w, y, (int)C, (int)H,
-                       (int)W, (int)in_row0, (int)in_rows, (int)out_row0, (int)out_rows, gate, gate_tag);
+                       (int)W, (int)in_row0, (int)in_rows, (int)out_row0, (int)out_rows, gate, gate_tag, interp, fr);
     MVBEV_CHECK_LAUNCH();
     return MVBEV_OK;
   }
   dim3 grid((unsigned)ceil_div(W, 64), (unsigned)out_rows, (unsigned)B);
 #define MVBEV_C1_LAUNCH(D)                                                                      \
   hipLaunchKernelGGL(conv3x3_cout1_kernel<D>, grid, dim3(64 * C1_WAVES), 0, s, x, w, y, (int)C,  \
-                     (int)H, (int)W, (int)in_row0, (int)in_rows, (int)out_row0, gate, gate_tag)
+                     (int)H, (int)W, (int)in_row0, (int)in_rows, (int)out_row0, gate, gate_tag, interp, fr)
   switch (dilation) {
     case 1: MVBEV_C1_LAUNCH(1); break;
     case 2: MVBEV_C1_LAUNCH(2); break;

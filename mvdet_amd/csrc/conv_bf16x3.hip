@@ -73,7 +73,8 @@ __global__ void pack_kernel(const float* __restrict__ w, __bf16* __restrict__ ou
 // k = forward output channel k; same layout as pack_kernel.
 __global__ void pack_dgrad_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int Cout_p,
                                   int Cf_out, int Cf_in, const int32_t* __restrict__ chan_map, int K_map,
-                                  int K_pad) {
+                                  int K_pad, const int32_t* gate, int32_t gate_tag) {
+  if (gate && *gate != gate_tag) return;  // the backward's non-finite guard: packed only when the flag fired
   const int n_cot = Cout_p / BN;
   const int64_t total = (int64_t)(K_pad / KC) * n_cot * 2 * WPART;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
@@ -719,8 +720,13 @@ constexpr int kC1rGroups = 4;
 __global__ __launch_bounds__(64 * kC1rGroups) void cout1_reduce_kernel(const float* __restrict__ p3, int nsets, int H,
                                                                       int W, int rows_p, int row0_p, int dil,
                                                                       float* __restrict__ map, int map_row0,
-                                                                      int map_rows) {
+                                                                      int map_rows, const int32_t* __restrict__ word,
+                                                                      int32_t word_tag, int32_t* __restrict__ flag,
+                                                                      int32_t flag_tag) {
   __shared__ float part[kC1rGroups][64];
+  // (ABI 12500) mvbev_flag_raise folded into the fast path's last launch: a non-finite parameter (the word of
+  // mvbev_params_nonfinite_f32) arms the frame's non-finite guard, whose gated exact path runs behind this kernel
+  if (word && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0 && *word == word_tag) *flag = flag_tag;
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane, qr = blockIdx.y, b = blockIdx.z;
   const int q = map_row0 + qr;
@@ -1370,9 +1376,11 @@ constexpr int W16 = 2 * WPART * 2 / 16;           // 16-B pieces per (chunk, cou
 // packed[o][i][kh][kw] = w[i][o][2 - kh][2 - kw], read from the forward weight w [K][Cin_w][3][3]
 // (o < Cout <= Cin_w) without a transposed copy.
 __global__ void pack_wino_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int Cout, int Cin_w,
-                                 const int32_t* __restrict__ chan_map, int K, int K_pad, bool swap) {
+                                 const int32_t* __restrict__ chan_map, int K, int K_pad, bool swap,
+                                 int32_t* __restrict__ nf_word, int32_t nf_tag) {
   const int n_cot = Cout / BN;
   const int64_t total = (int64_t)(K_pad / KC) * n_cot * 3 * 2 * BN * SB;  // columns
+  bool bad = false;  // (nf_word: the parameters' non-finite scan rides on the pack, which reads every mapped weight)
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t r = i;
     const int j = r % SB; r /= SB;
@@ -1392,6 +1400,7 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, __bf16* __restrict
       const float* g = w + ((int64_t)ci * Cin_w + cot * BN + co) * 9 + (2 - kw);  // reversed taps
       g0 = g[6], g1 = g[3], g2 = g[0];
     }
+    bad = bad || !(isfinite(g0) && isfinite(g1) && isfinite(g2));
     const double u[wino::NXI] = {0.5 * g0, -0.5 * (g0 + g1 + g2), (g1 - g0 - g2) / 6.0,
                                  (g0 + 2.0 * g1 + 4.0 * g2) / 6.0, g2};
     // element (part, tap = 3 xi + kw, sub, co, j) of the (chunk, cot) block
@@ -1405,6 +1414,7 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, __bf16* __restrict
       o[(int64_t)(wino::NTAP + tap) * KC * BN] = (__bf16)(v - (float)hi);
     }
   }
+  if (nf_word && bad) *nf_word = nf_tag;
 }
 
 struct WinoRowsArgs {
@@ -2401,8 +2411,18 @@ int mvbev_pack_conv3x3_weight_bf16x3(const float* w, int64_t Cout, int64_t Cin_w
   return MVBEV_OK;
 }
 
+int mvbev_pack_conv3x3_dgrad_bf16x3_gated(const float* w, int64_t Cout_w, int64_t Cin_w, const int32_t* chan_map,
+                                          int64_t K_out, void* w_packed, const int32_t* gate, int32_t gate_tag,
+                                          void* stream);
+
 int mvbev_pack_conv3x3_dgrad_bf16x3(const float* w, int64_t Cout_w, int64_t Cin_w, const int32_t* chan_map,
                                     int64_t K_out, void* w_packed, void* stream) {
+  return mvbev_pack_conv3x3_dgrad_bf16x3_gated(w, Cout_w, Cin_w, chan_map, K_out, w_packed, nullptr, 0, stream);
+}
+
+int mvbev_pack_conv3x3_dgrad_bf16x3_gated(const float* w, int64_t Cout_w, int64_t Cin_w, const int32_t* chan_map,
+                                          int64_t K_out, void* w_packed, const int32_t* gate, int32_t gate_tag,
+                                          void* stream) {
   using namespace mvbev;
   if (!w || !w_packed) return MVBEV_ERR_NULL;
   if (Cout_w <= 0 || Cin_w <= 0 || K_out <= 0) return MVBEV_ERR_RANK;
@@ -2413,7 +2433,7 @@ int mvbev_pack_conv3x3_dgrad_bf16x3(const float* w, int64_t Cout_w, int64_t Cin_
   const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 8192);
   hipLaunchKernelGGL(b3::pack_dgrad_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w,
                      static_cast<__bf16*>(w_packed), (int)cout_p, (int)Cout_w, (int)Cin_w, chan_map,
-                     (int)K_out, (int)k_pad);
+                     (int)K_out, (int)k_pad, gate, gate_tag);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }
@@ -2484,10 +2504,21 @@ int mvbev_conv3x3_bf16x3_cout1_partials(const void* x, const mvbev_conv_desc* de
                          nullptr, nullptr, 0, stream, nullptr, 1, w3, static_cast<float*>(partials));
 }
 
+int mvbev_cout1_reduce_partials_ex(const void* partials, const mvbev_conv_desc* desc, int64_t Cout, int dilation3,
+                                   float* map, int64_t map_row0, int64_t map_rows, const int32_t* word,
+                                   int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream);
+
 int mvbev_cout1_reduce_partials(const void* partials, const mvbev_conv_desc* desc, int64_t Cout, int dilation3,
                                 float* map, int64_t map_row0, int64_t map_rows, void* stream) {
+  return mvbev_cout1_reduce_partials_ex(partials, desc, Cout, dilation3, map, map_row0, map_rows, nullptr, 0, nullptr,
+                                        0, stream);
+}
+
+int mvbev_cout1_reduce_partials_ex(const void* partials, const mvbev_conv_desc* desc, int64_t Cout, int dilation3,
+                                   float* map, int64_t map_row0, int64_t map_rows, const int32_t* word,
+                                   int32_t word_tag, int32_t* flag, int32_t flag_tag, void* stream) {
   using namespace mvbev::b3;
-  if (!partials || !desc || !map) return MVBEV_ERR_NULL;
+  if (!partials || !desc || !map || (word && !flag)) return MVBEV_ERR_NULL;
   if (dilation3 < 1) return MVBEV_ERR_DILATION;
   if (map_rows <= 0 || Cout <= 0 || desc->B <= 0 || desc->W <= 0 || desc->out_rows <= 0) return MVBEV_ERR_RANK;
   if (Cout % BN != 0) return MVBEV_ERR_SHAPE;
@@ -2500,7 +2531,8 @@ int mvbev_cout1_reduce_partials(const void* partials, const mvbev_conv_desc* des
   const dim3 grid((unsigned)mvbev::ceil_div(desc->W, 64), (unsigned)map_rows, (unsigned)desc->B);
   hipLaunchKernelGGL(cout1_reduce_kernel, grid, dim3(64 * kC1rGroups), 0, mvbev::as_stream(stream),
                      static_cast<const float*>(partials), (int)(2 * (Cout / BN)), (int)desc->H, (int)desc->W,
-                     (int)desc->out_rows, (int)desc->out_row0, dilation3, map, (int)map_row0, (int)map_rows);
+                     (int)desc->out_rows, (int)desc->out_row0, dilation3, map, (int)map_row0, (int)map_rows, word,
+                     word_tag, flag, flag_tag);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }
@@ -2539,8 +2571,16 @@ size_t mvbev_conv3x3_packed_bytes_wino(int64_t Cout, int64_t K) {
          mvbev::b3::wino::W16 * 16;
 }
 
+int mvbev_pack_conv3x3_weight_wino_ex(const float* w, int64_t Cout, int64_t Cin_w, const int32_t* chan_map, int64_t K,
+                                      void* w_packed, int32_t* nf_word, int32_t nf_tag, void* stream);
+
 int mvbev_pack_conv3x3_weight_wino(const float* w, int64_t Cout, int64_t Cin_w, const int32_t* chan_map, int64_t K,
                                    void* w_packed, void* stream) {
+  return mvbev_pack_conv3x3_weight_wino_ex(w, Cout, Cin_w, chan_map, K, w_packed, nullptr, 0, stream);
+}
+
+int mvbev_pack_conv3x3_weight_wino_ex(const float* w, int64_t Cout, int64_t Cin_w, const int32_t* chan_map, int64_t K,
+                                      void* w_packed, int32_t* nf_word, int32_t nf_tag, void* stream) {
   using namespace mvbev;
   if (!w || !w_packed) return MVBEV_ERR_NULL;
   if (Cout <= 0 || Cin_w <= 0 || K <= 0) return MVBEV_ERR_RANK;
@@ -2550,7 +2590,7 @@ int mvbev_pack_conv3x3_weight_wino(const float* w, int64_t Cout, int64_t Cin_w, 
   const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 8192);
   hipLaunchKernelGGL(b3::pack_wino_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w,
                      static_cast<__bf16*>(w_packed), (int)Cout, (int)Cin_w, chan_map, (int)K,
-                     (int)round_up(K, b3::KC), false);
+                     (int)round_up(K, b3::KC), false, nf_word, nf_tag);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }
@@ -2565,7 +2605,7 @@ int mvbev_pack_conv3x3_weight_wino_dgrad(const float* w, int64_t Cout_f, int64_t
   const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 8192);
   hipLaunchKernelGGL(b3::pack_wino_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w,
                      static_cast<__bf16*>(w_packed), (int)Cout, (int)Cin_f, nullptr, (int)Cout_f,
-                     (int)round_up(Cout_f, b3::KC), true);
+                     (int)round_up(Cout_f, b3::KC), true, nullptr, 0);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }

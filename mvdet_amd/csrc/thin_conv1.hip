@@ -9,7 +9,9 @@
 // stages the N + 2 channels of the tile grown by one pixel in LDS: one warp sample (warp_common.h's warp_coord, the
 // blend of warp_tile_kernel, corner loads through L1 / L2) or coord value per (channel, halo pixel), zero outside
 // the grid.  A view none of whose staged samples is inside its source (or non-finite) is marked dead: geometry
-// only, and it adds exact zeros.  Phase 2: one thread per pixel, 8 output channels per pass; the weights are
+// only, and it adds exact zeros — unless its w1 columns hold a NaN / inf (bit v of the device word w_mask,
+// thin_conv1_weight_mask_kernel, once per weight version): 0 * NaN is NaN in the reference, so such a view is
+// evaluated over every tile.  Phase 2: one thread per pixel, 8 output channels per pass; the weights are
 // wave-uniform and come through scalar loads, every tap is multiplied (a NaN sample reaches its 3 x 3
 // neighbourhood in every channel), the sum runs in a fixed order: per output channel three partial sums over the
 // input channels in order — taps (0, 2, 4, 6) from the bias, taps (1, 3, 5, 7), tap 8 — added at the end (two
@@ -83,7 +85,8 @@ __device__ inline float tc_sample(const float* __restrict__ base, int64_t sH, co
 // their wave-uniform loads become scalar loads)
 __global__ __launch_bounds__(kTcThreads) void thin_conv1_fwd_kernel(const TcArgs ta, const float* __restrict__ w1,
                                                                    const float* __restrict__ b1,
-                                                                   void* __restrict__ y1, float* __restrict__ xwp) {
+                                                                   void* __restrict__ y1, float* __restrict__ xwp,
+                                                                   const int32_t* __restrict__ w_mask) {
   __shared__ float xs[kTcMaxCh][kTcHH][kTcHW];
   __shared__ int live[kTcMaxCh];
   const WarpArgs& a = ta.w;
@@ -96,7 +99,8 @@ __global__ __launch_bounds__(kTcThreads) void thin_conv1_fwd_kernel(const TcArgs
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int r0 = ty * kTcTH, u0 = tx * kTcTW;
 
-  if (tid < kTcMaxCh) live[tid] = tid >= N;  // the coord channels always count
+  // the coord channels always count, and a view whose weights are non-finite (0 * NaN = NaN)
+  if (tid < kTcMaxCh) live[tid] = tid >= N || (w_mask && ((*w_mask >> tid) & 1));
   __syncthreads();
   // phase 1
   for (int it = tid; it < nch * (kTcHH * kTcHW); it += kTcThreads) {
@@ -170,6 +174,22 @@ __global__ __launch_bounds__(kTcThreads) void thin_conv1_fwd_kernel(const TcArgs
       for (int j = 0; j < 8; ++j) out[j * npix] = acc[j];
     }
   }
+}
+
+// bit v of *mask = w1[:, v] (v < N) holds a NaN / inf.  One workgroup: the word is written whole by every launch.
+__global__ __launch_bounds__(1024) void thin_conv1_weight_mask_kernel(const float* __restrict__ w1, int N, int64_t n,
+                                                                      int32_t* __restrict__ mask) {
+  __shared__ int m;
+  if (threadIdx.x == 0) m = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int64_t i = threadIdx.x; i < n; i += 1024) {
+    const int c = (int)((i / 9) % (N + 2));
+    if (c < N && !isfinite(w1[i])) mine |= 1 << c;
+  }
+  if (mine) atomicOr(&m, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) *mask = m;
 }
 
 struct TcBwdArgs {
@@ -335,9 +355,31 @@ static int tc_check_sizes(int64_t nviews, int64_t B, int64_t Cout, int64_t Ho, i
 
 extern "C" {
 
+int mvbev_thin_conv1_forward_f32_ex(const mvbev_warp_view* views, int nviews, int64_t B, int64_t H, int64_t W,
+                                    int64_t Ho, int64_t Wo, const float* w1, const float* b1, int64_t Cout, void* y1,
+                                    int y1_layout, float* xw, const int32_t* w_mask, void* stream);
+
 int mvbev_thin_conv1_forward_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t H, int64_t W, int64_t Ho,
                                  int64_t Wo, const float* w1, const float* b1, int64_t Cout, void* y1, int y1_layout,
                                  float* xw, void* stream) {
+  return mvbev_thin_conv1_forward_f32_ex(views, nviews, B, H, W, Ho, Wo, w1, b1, Cout, y1, y1_layout, xw, nullptr,
+                                         stream);
+}
+
+int mvbev_thin_conv1_weight_mask(const float* w1, int nviews, int64_t Cout, int32_t* mask, void* stream) {
+  using namespace mvbev;
+  if (!w1 || !mask) return MVBEV_ERR_NULL;
+  if (nviews <= 0 || Cout <= 0) return MVBEV_ERR_RANK;
+  if (nviews > kWarpMaxViews || Cout > INT32_MAX / (9 * (kWarpMaxViews + 2))) return MVBEV_ERR_SHAPE;
+  hipLaunchKernelGGL(thin_conv1_weight_mask_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w1, nviews,
+                     Cout * (nviews + 2) * 9, mask);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
+int mvbev_thin_conv1_forward_f32_ex(const mvbev_warp_view* views, int nviews, int64_t B, int64_t H, int64_t W,
+                                    int64_t Ho, int64_t Wo, const float* w1, const float* b1, int64_t Cout, void* y1,
+                                    int y1_layout, float* xw, const int32_t* w_mask, void* stream) {
   using namespace mvbev;
   if (!views || !w1 || !y1) return MVBEV_ERR_NULL;
   if (H <= 0 || W <= 0) return MVBEV_ERR_RANK;
@@ -366,7 +408,7 @@ int mvbev_thin_conv1_forward_f32(const mvbev_warp_view* views, int nviews, int64
   a.nwg = (int)(B * tiles_x * tiles_y * cslices);
   ta.Cout = (int)Cout, ta.cslices = (int)cslices, ta.split = y1_layout == MVBEV_LAYOUT_SPLIT_BF16;
   hipLaunchKernelGGL(thin_conv1_fwd_kernel, dim3((unsigned)a.nwg), dim3(kTcThreads), 0, as_stream(stream), ta, w1, b1, y1,
-                     xw);
+                     xw, w_mask);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }

@@ -178,7 +178,9 @@ __global__ __launch_bounds__(kWave) void warp_sum_head_fwd_kernel(const ShArgs s
       if (nan) part = __builtin_nanf("");  // (Cm < 4 lanes' worth: every lane, not only those with a channel)
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-      if (lane == 0) sa.map[((int64_t)b * Ho + v) * Wo + u] = part;
+      // no_joint_conv_variant.py:81 interpolates the map to its own size: the identity, except that torch's lerp
+      // x + 0 * (x' - x) turns +-inf (a non-finite w2, bias or coord weight) into NaN at that pixel
+      if (lane == 0) sa.map[((int64_t)b * Ho + v) * Wo + u] = isinf(part) ? __builtin_nanf("") : part;
     }
     if (sa.hidden) {
       __syncthreads();  // one wave: orders the LDS stores above before the transposed reads

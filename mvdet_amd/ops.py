@@ -285,10 +285,13 @@ def fill_coord_map(dst: torch.Tensor) -> torch.Tensor:
 
 
 def coord_term(weight: torch.Tensor, bias: Optional[torch.Tensor], coord_c0: int, hw,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, scan=None, extra=()) -> torch.Tensor:
     """conv1's coord term [Cout, H, W] (``mvbev_coord_term_f32``): ``bias`` + conv2d of the coord map
     (``persp_trans_detector.py:103-112``, zero padding 1) with ``weight[:, coord_c0:coord_c0 + 2]`` —
-    the input-independent part of conv1 (``:51`` over ``:77``'s concat)."""
+    the input-independent part of conv1 (``:51`` over ``:77``'s concat).  ``scan`` = (word, tag): the parameters'
+    non-finite scan rides on the launch (``mvbev_coord_term_f32_ex``) — the tag is stored into the word when the
+    term is non-finite (a NaN / inf coord weight or bias) or one of up to two small contiguous fp32 tensors
+    ``extra`` holds a NaN / inf."""
     _require_cuda(weight)
     if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.dtype != torch.float32:
         raise ValueError("weight must be a float32 [Cout, Cin, 3, 3] tensor")
@@ -302,9 +305,17 @@ def coord_term(weight: torch.Tensor, bias: Optional[torch.Tensor], coord_c0: int
         out = torch.empty((cout, H, W), dtype=torch.float32, device=w.device)
     elif tuple(out.shape) != (cout, H, W) or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous float32 [{cout}, {H}, {W}] tensor")
-    st = _native.load().mvbev_coord_term_f32(w.data_ptr(), cin, int(coord_c0), 0 if b is None else b.data_ptr(),
-                                             cout, H, W, out.data_ptr(), _stream(w))
-    _native.check(st, "mvbev_coord_term_f32")
+    ex = [e.detach() for e in extra]
+    if len(ex) > 2 or any(e.dtype != torch.float32 or not e.is_contiguous() or e.device != w.device for e in ex):
+        raise ValueError("extra: at most two contiguous float32 tensors on the weight's device")
+    ex += [None] * (2 - len(ex))
+    sp, stag = _gate(scan)
+    st = _native.load().mvbev_coord_term_f32_ex(w.data_ptr(), cin, int(coord_c0), 0 if b is None else b.data_ptr(),
+                                                cout, H, W, out.data_ptr(), sp, stag,
+                                                *[v for e in ex for v in ((None, 0) if e is None or scan is None
+                                                                          else (e.data_ptr(), e.numel()))],
+                                                _stream(w))
+    _native.check(st, "mvbev_coord_term_f32_ex")
     return out
 
 
@@ -444,6 +455,43 @@ def zero_gated_(t: torch.Tensor, gate) -> torch.Tensor:
     return t
 
 
+def params_nonfinite(params, word: torch.Tensor, tag: int) -> None:
+    """``mvbev_params_nonfinite_f32``: ``tag`` into the device int32 ``word`` when any value of the fp32 tensors
+    ``params`` (at most 8) is NaN / inf — one launch, no host sync, nothing read back."""
+    ps = [p.detach() for p in params]
+    _require_cuda(word, *ps)
+    if any(p.dtype != torch.float32 or p.device != word.device for p in ps):
+        raise ValueError("the parameters must be float32 tensors on the word's device")
+    ps = [p if p.is_contiguous() else p.contiguous() for p in ps]  # (a copy lives until the launch, in stream order)
+    wp, wt = _gate((word, tag))
+    ptrs = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
+    counts = (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps])
+    st = _native.load().mvbev_params_nonfinite_f32(ptrs, counts, len(ps), wp, wt, _stream(word))
+    _native.check(st, "mvbev_params_nonfinite_f32")
+
+
+def flag_raise(word_gate, flag_gate) -> None:
+    """``mvbev_flag_raise``: store ``flag_gate = (flag, tag)``'s tag into its flag when the device word of
+    ``word_gate = (word, tag)`` holds its tag (one thread; no host sync either way)."""
+    wp, wt = _gate(word_gate)
+    fp, ft = _gate(flag_gate)
+    st = _native.load().mvbev_flag_raise(wp, wt, fp, ft, _stream(flag_gate[0]))
+    _native.check(st, "mvbev_flag_raise")
+
+
+def mask_gated(mask: torch.Tensor, out: torch.Tensor, gate) -> torch.Tensor:
+    """``mvbev_mask_gated_u32``: ``out`` = the int32 tile mask ``mask`` when the device flag of ``gate = (flag, tag)``
+    holds tag, else all zero — a launch given ``out`` as its tile mask does work only when the flag fired."""
+    _require_cuda(mask, out)
+    if (mask.dtype != torch.int32 or out.dtype != torch.int32 or out.numel() != mask.numel()
+            or not mask.is_contiguous() or not out.is_contiguous()):
+        raise ValueError("mask and out must be contiguous int32 tensors of one size")
+    gp, gt = _gate(gate)
+    st = _native.load().mvbev_mask_gated_u32(mask.data_ptr(), mask.numel(), out.data_ptr(), gp, gt, _stream(mask))
+    _native.check(st, "mvbev_mask_gated_u32")
+    return out
+
+
 def is_channels_last_source(x: torch.Tensor) -> bool:
     """True when the fused warps take ``x`` [B,C,H,W] fp32 in their channels-last form (ABI 11700: unit
     channel stride, whole 32-channel groups, strides multiples of 4 floats, 16-B aligned)."""
@@ -548,7 +596,10 @@ class PackedConv3x3:
         _native.check(st, "mvbev_pack_conv3x3_weight_f32_gated")
         return self.packed
 
-    def get(self, weight: torch.Tensor) -> torch.Tensor:
+    def get(self, weight: torch.Tensor, scan=None) -> torch.Tensor:
+        """``scan`` = (word, tag, done): when this call packs the F(3,3) row-Winograd weights, the parameters'
+        non-finite scan rides on the pack (``mvbev_pack_conv3x3_weight_wino_ex``: the tag into the word when a
+        weight it reads is NaN / inf) and ``done()`` is called; a cached pack leaves the scan to the caller."""
         _require_cuda(weight)
         lib = _native.load()
         # the packed layout belongs to the library that packed it (A/B runs swap libraries)
@@ -579,9 +630,12 @@ class PackedConv3x3:
             elif self.wino:
                 n = lib.mvbev_conv3x3_packed_bytes_wino(cout, K)
                 packed = torch.empty(n // 2, dtype=torch.bfloat16, device=weight.device)
-                st = lib.mvbev_pack_conv3x3_weight_wino(w.data_ptr(), cout, cin, cmap, K, packed.data_ptr(),
-                                                        _stream(packed))
-                _native.check(st, "mvbev_pack_conv3x3_weight_wino")
+                sp, stag = _gate(None if scan is None else scan[:2])
+                st = lib.mvbev_pack_conv3x3_weight_wino_ex(w.data_ptr(), cout, cin, cmap, K, packed.data_ptr(),
+                                                           sp, stag, _stream(packed))
+                _native.check(st, "mvbev_pack_conv3x3_weight_wino_ex")
+                if scan is not None:
+                    scan[2]()
             else:
                 n = lib.mvbev_conv3x3_packed_bytes_bf16x3(cout, K)
                 packed = torch.empty(n // 2, dtype=torch.bfloat16, device=weight.device)
@@ -1002,8 +1056,12 @@ def conv3x3(x: torch.Tensor, packed: torch.Tensor, cout: int, bias: Optional[tor
 
 def conv3x3_cout1(x: torch.Tensor, weight: torch.Tensor, dilation: int, H: Optional[int] = None,
                   in_row0: int = 0, out_row0: int = 0, out_rows: Optional[int] = None,
-                  out: Optional[torch.Tensor] = None, gate=None) -> torch.Tensor:
-    """``conv2d(x, weight[1,C,3,3], padding=d, dilation=d)`` (no bias).
+                  out: Optional[torch.Tensor] = None, gate=None, same_size_interp: bool = False,
+                  raise_flag=None) -> torch.Tensor:
+    """``conv2d(x, weight[1,C,3,3], padding=d, dilation=d)`` (no bias).  ``same_size_interp``: followed by
+    ``persp_trans_detector.py:82``'s ``F.interpolate`` to the same size — the identity, except that torch's lerp
+    turns +-inf into NaN (``MVBEV_COUT1_SAME_SIZE_INTERP``: the exact path's map).  ``raise_flag``:
+    ``((word, tag), (flag, tag))`` — ``flag_raise`` folded into this launch.
 
     ``x`` [B,C,rows,W] holds global rows ``[in_row0, in_row0+rows)`` of an ``H``-row image
     (default: the whole image); returns rows ``[out_row0, out_row0+out_rows)`` → [B,1,out_rows,W].
@@ -1023,9 +1081,13 @@ def conv3x3_cout1(x: torch.Tensor, weight: torch.Tensor, dilation: int, H: Optio
     elif tuple(out.shape) != (B, 1, out_rows, W) or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous fp32 [{B},1,{out_rows},{W}] tensor")
     gp, gt = _gate(gate)
-    st = _native.load().mvbev_conv3x3_cout1_f32(x.data_ptr(), B, C, H, W, in_row0, rows, out_row0, out_rows,
-                                                w.data_ptr(), int(dilation), out.data_ptr(), gp, gt, _stream(x))
-    _native.check(st, "mvbev_conv3x3_cout1_f32")
+    flags = _native.COUT1_SAME_SIZE_INTERP if same_size_interp else 0
+    wp, wt = _gate(None if raise_flag is None else raise_flag[0])
+    fp, ft = _gate(None if raise_flag is None else raise_flag[1])
+    st = _native.load().mvbev_conv3x3_cout1_f32_ex(x.data_ptr(), B, C, H, W, in_row0, rows, out_row0, out_rows,
+                                                   w.data_ptr(), int(dilation), out.data_ptr(), flags, gp, gt,
+                                                   wp, wt, fp, ft, _stream(x))
+    _native.check(st, "mvbev_conv3x3_cout1_f32_ex")
     return out
 
 
@@ -1262,16 +1324,20 @@ def conv3x3_wino43_then_cout1_partials(t: torch.Tensor, desc, packed: torch.Tens
 
 
 def cout1_from_partials(partials: torch.Tensor, desc, cout: int, dilation3: int, map_row0: int, map_rows: int,
-                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        out: Optional[torch.Tensor] = None, raise_flag=None) -> torch.Tensor:
     """``conv2d(act(y), weight3, padding=d3, dilation=d3)`` rows ``[map_row0, map_row0+map_rows)``
-    → [B,1,map_rows,W] from ``conv3x3_then_cout1_partials``' partials (fixed summation order)."""
+    → [B,1,map_rows,W] from ``conv3x3_then_cout1_partials``' partials (fixed summation order).  ``raise_flag``:
+    ``((word, tag), (flag, tag))`` — ``flag_raise`` folded into this launch."""
     _require_cuda(partials)
     B, W = desc.B, desc.W
     if out is None:
         out = torch.empty((B, 1, map_rows, W), dtype=torch.float32, device=partials.device)
-    st = _native.load().mvbev_cout1_reduce_partials(partials.data_ptr(), ctypes.byref(desc), int(cout), int(dilation3),
-                                                     out.data_ptr(), int(map_row0), int(map_rows), _stream(partials))
-    _native.check(st, "mvbev_cout1_reduce_partials")
+    wp, wt = _gate(None if raise_flag is None else raise_flag[0])
+    fp, ft = _gate(None if raise_flag is None else raise_flag[1])
+    st = _native.load().mvbev_cout1_reduce_partials_ex(partials.data_ptr(), ctypes.byref(desc), int(cout),
+                                                        int(dilation3), out.data_ptr(), int(map_row0), int(map_rows),
+                                                        wp, wt, fp, ft, _stream(partials))
+    _native.check(st, "mvbev_cout1_reduce_partials_ex")
     return out
 
 
@@ -1407,6 +1473,18 @@ def warp_views_adjoint(grad_outs, plans, grad_srcs, accumulate: bool = False, pi
     _native.check(st, "mvbev_warp_views_adjoint")
 
 
+class GatedDgradPack:
+    """What ``PackedDgrad3x3.get_gated`` returns: the gated pack's buffer behind ``PackedDgrad3x3``'s interface
+    (``cout_p``, ``get``), for ``conv3x3_dgrad``."""
+
+    def __init__(self, cout_p: int, packed: torch.Tensor):
+        self.cout_p = cout_p
+        self.packed = packed
+
+    def get(self, weight: torch.Tensor) -> torch.Tensor:
+        return self.packed
+
+
 class PackedDgrad3x3:
     """bf16x3-packed weights of a 3x3 conv's DATA gradient (transposed, flipped taps:
     ``mvbev_pack_conv3x3_dgrad_bf16x3``).  Output channel o of the dgrad conv = forward input
@@ -1422,6 +1500,7 @@ class PackedDgrad3x3:
         self._key = None
         self.packed: Optional[torch.Tensor] = None
         self._map_dev: Optional[torch.Tensor] = None
+        self._gated: Optional[GatedDgradPack] = None
 
     def get(self, weight: torch.Tensor) -> torch.Tensor:
         _require_cuda(weight)
@@ -1447,6 +1526,31 @@ class PackedDgrad3x3:
             self.packed, self._key = packed, key
         return self.packed
 
+    def get_gated(self, weight: torch.Tensor, gate) -> GatedDgradPack:
+        """These weights packed only when the device flag of ``gate = (flag, tag)`` holds tag, enqueued on EVERY
+        call into a buffer of its own (``mvbev_pack_conv3x3_dgrad_bf16x3_gated``; a skipped pack is never cached),
+        as a ``GatedDgradPack`` — for a launch gated on the same flag."""
+        _require_cuda(weight)
+        lib = _native.load()
+        cout_w, cin_w, kh, kw = weight.shape
+        if (kh, kw) != (3, 3) or weight.dtype != torch.float32 or cout_w % KC or not weight.is_contiguous():
+            raise ValueError("expected a contiguous float32 [Cout,Cin,3,3] weight with Cout % 8 == 0")
+        if self.chan_map is None and self.k_out > cin_w:
+            raise ValueError(f"k_out={self.k_out} exceeds the weight's {cin_w} input channels")
+        if self.chan_map is not None and (self._map_dev is None or self._map_dev.device != weight.device):
+            self._map_dev = torch.tensor(self.chan_map, dtype=torch.int32, device=weight.device)
+        g = self._gated
+        n = lib.mvbev_conv3x3_packed_bytes_bf16x3(self.cout_p, cout_w)
+        if g is None or g.packed.numel() != n // 2 or g.packed.device != weight.device:
+            g = self._gated = GatedDgradPack(self.cout_p, torch.empty(n // 2, dtype=torch.bfloat16,
+                                                                      device=weight.device))
+        gp, gt = _gate(gate)
+        st = lib.mvbev_pack_conv3x3_dgrad_bf16x3_gated(weight.detach().data_ptr(), cout_w, cin_w,
+                                                       None if self._map_dev is None else self._map_dev.data_ptr(),
+                                                       self.k_out, g.packed.data_ptr(), gp, gt, _stream(g.packed))
+        _native.check(st, "mvbev_pack_conv3x3_dgrad_bf16x3_gated")
+        return g
+
 
 def dgrad_schedule(B: int, cout_p: int, H: int, W: int, K: int, out_mask: Optional[torch.Tensor],
                    cot_per_group: int, device, split: bool = True):
@@ -1462,7 +1566,7 @@ def dgrad_schedule(B: int, cout_p: int, H: int, W: int, K: int, out_mask: Option
     return schedule.plan(blocks, cus, device, split=split)
 
 
-def conv3x3_dgrad(dy: torch.Tensor, packed: PackedDgrad3x3, weight: torch.Tensor, dilation: int,
+def conv3x3_dgrad(dy: torch.Tensor, packed: "PackedDgrad3x3 | GatedDgradPack", weight: torch.Tensor, dilation: int,
                   out: Optional[torch.Tensor] = None, out_mask: Optional[torch.Tensor] = None,
                   cot_per_group: int = 1, sched=None) -> torch.Tensor:
     """Data gradient of a 3x3 stride-1 conv (padding = dilation): dy [B,Cout_w,H,W] fp32

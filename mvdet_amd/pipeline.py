@@ -27,6 +27,7 @@ allocates in steady state, copies to the host or synchronises.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -243,6 +244,10 @@ class ProjectFuse:
         self.pack1w43 = ops.PackedConv3x3(chan_map, "bf16x3", wino=True, form=4) if self.wino43 else None
         self.pack2w43 = ops.PackedConv3x3(None, "bf16x3", wino=True, form=4) if self.wino43 else None
         self._cus: Dict[str, int] = {}
+        self._param_words: Dict[str, SimpleNamespace] = {}  # per device: the parameters' non-finite word (param_word)
+        self._scan_state: Optional[SimpleNamespace] = None  # of the frame in flight (fuse), for its packs' scans
+        # conv1's pack reads every view channel of w1 (not so in the partial-sum engines' channel slices)
+        self._pack1_covers = sorted(c for c in chan_map if c >= 0) == list(range(nc))
 
     def wino43_pays(self, rows: int, B: int, device, deep: bool = False) -> bool:
         """F(4,3) over ``rows`` output rows (whole grid): enabled and its 16-row tiles waste at most 3 % of the rows;
@@ -491,13 +496,79 @@ class ProjectFuse:
 
     # -- coord term (a2 folded into conv1) --------------------------------------------------
     def coord_term(self, conv1: torch.nn.Conv2d) -> torch.Tensor:
-        """[512, Ho, Wo]: bias + conv(coord channels) for the current conv1 parameters."""
+        """[512, Ho, Wo]: bias + conv(coord channels) for the current conv1 parameters.  With the frame's parameter
+        scan open (``_scan``) the launch also looks at what it reads and through the small parameters b2 and w3."""
         w, b = conv1.weight, conv1.bias
         key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
         if key != self._coord_key:  # (ABI 12300: one VALU pass; was an fp32-MFMA conv over a padded coord input)
-            self._coord_term = ops.coord_term(w, b, self.coord_c0, self.grid_hw)  # (fresh: in-flight readers)
+            extra = [(n, t) for n, t in (self._scan_state.extra if self._scan_state is not None else ())
+                     if t is not None and t.is_contiguous()]
+            scan = self._scan("w1_coord", "b1", *[n for n, _ in extra])
+            self._coord_term = ops.coord_term(w, b, self.coord_c0, self.grid_hw,  # (fresh: in-flight readers)
+                                              scan=None if scan is None else scan[:2],
+                                              extra=[t for _, t in extra] if scan is not None else ())
+            if scan is not None:
+                scan[2]()
             self._coord_key = key
         return self._coord_term
+
+    def _param_state(self, map_classifier):
+        """The state of the parameters' non-finite word on their device: a new weight version — keyed on the
+        parameters' ``(data_ptr, _version)`` as the packs and the coord term are — takes a fresh tag (so the word
+        needs no reset) and forgets what was scanned."""
+        ps = [map_classifier[0].weight, map_classifier[0].bias, map_classifier[2].weight, map_classifier[2].bias,
+              map_classifier[4].weight]
+        key = tuple(None if p is None else (p.data_ptr(), p._version) for p in ps)
+        dev = ps[0].device
+        st = self._param_words.get(str(dev))
+        if st is None:
+            st = self._param_words[str(dev)] = SimpleNamespace(word=torch.zeros(1, dtype=torch.int32, device=dev),
+                                                               tag=0, key=None, covered=set(), done=False)
+        if key != st.key:
+            st.tag = st.tag % 0x7FFFFFFE + 1
+            if st.tag == 1:
+                st.word.zero_()
+            st.key, st.covered, st.done = key, set(), False
+        return st
+
+    def _scan(self, *names):
+        """``scan`` argument for a pack / the coord term of the frame in flight (``fuse``): (word, tag, done) while
+        this weight version's scan is open — the launch then looks at the parameters ``names`` on its way — else
+        None."""
+        st = self._scan_state
+        if st is None or st.done:
+            return None
+        return st.word, st.tag, lambda: st.covered.update(names)
+
+    def param_word(self, map_classifier) -> Tuple[torch.Tensor, int]:
+        """(word, tag): the device int32 ``word`` holds ``tag`` when a parameter of ``map_classifier`` (w1, b1, w2,
+        b2, w3) is NaN / inf.  Once per weight version, nothing read back (in training the weights change every
+        step: a sync per version would be a sync per step).  Inside ``fuse`` the scan rides on launches that read
+        the weights anyway when they change — conv1's and conv2's F(3,3) row-Winograd packs (w1's view channels,
+        w2) and the coord term (w1's coord channels, b1, and b2 and w3 as its two small extra arrays) — so a
+        training step pays no launch and no pass over the weights for it; whatever those launches did not cover
+        (cached packs, F(4,3) packs, a call outside ``fuse``) is scanned here in one launch
+        (``ops.params_nonfinite``)."""
+        st = self._param_state(map_classifier)
+        if not st.done:
+            c1, c2, c3 = map_classifier[0], map_classifier[2], map_classifier[4]
+            left = []
+            if not {"w1_views", "w1_coord"} <= st.covered:
+                left.append(c1.weight)
+            left += [t for name, t in (("b1", c1.bias), ("w2", c2.weight), ("b2", c2.bias), ("w3", c3.weight))
+                     if t is not None and name not in st.covered]
+            if left:
+                ops.params_nonfinite(left, st.word, st.tag)
+            st.done = True
+        return st.word, st.tag
+
+    def _raise_from_params(self, map_classifier, flag) -> None:
+        """Arm the non-finite guard ``flag = (flag, tag)`` of a frame from the parameters (``param_word``): one
+        one-thread launch (the partial-sum multi-GPU mode; inference and the training forward fold it into conv3's
+        launch, ``conv3_from_partials`` / ``conv3``).  The fast path cannot keep the reference's pattern under a non-finite
+        weight — the frustum mask never multiplies a masked view's w1 columns (the reference: 0 * NaN = NaN), the
+        hi/lo split of inf is (inf, NaN) and G w takes differences of weights — the gated exact path can."""
+        ops.flag_raise(self.param_word(map_classifier), flag)
 
     def _sk_ws(self, desc, device) -> Optional[torch.Tensor]:
         """Split-K-tail scratch for a bf16x3 conv (grown once, then reused: the convs of a
@@ -653,8 +724,8 @@ class ProjectFuse:
         ws.t1_valid = (a1, b1) == (0, self.grid_hw[0])
         if mark:
             mark("conv1_wino")  # between the transform and the conv (bench.py's stage events)
-        return ops.conv3x3_wino(ws.wino_t, d1, self.pack1w.get(conv1.weight), self.mid, init=init, relu=True,
-                                out=ws.y1, group_mask=gm,
+        p1 = self.pack1w.get(conv1.weight, scan=self._scan("w1_views") if self._pack1_covers else None)
+        return ops.conv3x3_wino(ws.wino_t, d1, p1, self.mid, init=init, relu=True, out=ws.y1, group_mask=gm,
                                 tile_order=self.conv1_order(ws.slab.device, a1, b1 - a1, B, grid=True))
 
     def conv1_form(self, ws: Workspace) -> int:
@@ -688,8 +759,8 @@ class ProjectFuse:
                 ws.wino_t2 = torch.zeros((tneed + 1) // 2, dtype=torch.bfloat16, device=ws.y1.device)
             ops.wino_rows(ws.y1, d2, ws.wino_t2, dilation=2)
             ws.t2_valid = (a1, b1) == (a2, b2) == (0, H)  # the backward's conv2 weight gradient reads it
-            return ops.conv3x3_wino_dil(ws.wino_t2, d2, self.pack2w.get(conv2.weight), self.mid, 2, bias=conv2.bias,
-                                        relu=True, out=ws.y2)
+            p2 = self.pack2w.get(conv2.weight, scan=self._scan("w2"))
+            return ops.conv3x3_wino_dil(ws.wino_t2, d2, p2, self.mid, 2, bias=conv2.bias, relu=True, out=ws.y2)
         p2 = self.pack2.get(conv2.weight)
         return ops.conv3x3_desc(ws.y1, d2, p2, self.mid, bias=conv2.bias, dilation=2, relu=True, out=ws.y2,
                                 workspace=self._sk_ws(d2, ws.y1.device))
@@ -726,7 +797,8 @@ class ProjectFuse:
             if ws.wino_t2 is None or ws.wino_t2.numel() * 2 < tneed:
                 ws.wino_t2 = torch.zeros((tneed + 1) // 2, dtype=torch.bfloat16, device=ws.y1.device)
             ops.wino_rows(ws.y1, d2, ws.wino_t2, dilation=2)
-            ops.conv3x3_wino_then_cout1_partials(ws.wino_t2, d2, self.pack2w.get(conv2.weight), self.mid,
+            p2 = self.pack2w.get(conv2.weight, scan=self._scan("w2"))
+            ops.conv3x3_wino_then_cout1_partials(ws.wino_t2, d2, p2, self.mid,
                                                  conv2.bias, 2, True, conv3.weight, ws.p3)
             return
         ops.conv3x3_then_cout1_partials(ws.y1, d2, self.pack2.get(conv2.weight), self.mid, conv2.bias, 2, True,
@@ -738,17 +810,19 @@ class ProjectFuse:
         return (self.wino_conv2 and ws.y1.dtype == torch.bfloat16
                 and self.nonfinite_views(ws.y1.device) == 0)
 
-    def conv3_from_partials(self, ws: Workspace, conv3: torch.nn.Conv2d) -> torch.Tensor:
-        """The rest of a9: map rows ``ws.band`` from the partials (fixed summation order)."""
+    def conv3_from_partials(self, ws: Workspace, conv3: torch.nn.Conv2d, raise_flag=None) -> torch.Tensor:
+        """The rest of a9: map rows ``ws.band`` from the partials (fixed summation order).  ``raise_flag``:
+        ``(param_word, frame flag)`` — the guard's raise from the parameters rides on this launch."""
         r0, r1 = ws.band
-        return ops.cout1_from_partials(ws.p3, self._conv2_desc(ws), self.mid, 4, r0, r1 - r0)
+        return ops.cout1_from_partials(ws.p3, self._conv2_desc(ws), self.mid, 4, r0, r1 - r0, raise_flag=raise_flag)
 
-    def conv3(self, ws: Workspace, conv3: torch.nn.Conv2d) -> torch.Tensor:
-        """a9: map = conv3x3_d4(y2) (Cout 1, no bias) on the output band → [B,1,rows,Wo]."""
+    def conv3(self, ws: Workspace, conv3: torch.nn.Conv2d, raise_flag=None) -> torch.Tensor:
+        """a9: map = conv3x3_d4(y2) (Cout 1, no bias) on the output band → [B,1,rows,Wo].  ``raise_flag``: as
+        ``conv3_from_partials``'s (the training forward)."""
         H = self.grid_hw[0]
         r0, r1 = ws.band
         return ops.conv3x3_cout1(ws.y2, conv3.weight, 4, H=H, in_row0=ws.y2_rows[0], out_row0=r0,
-                                 out_rows=r1 - r0)
+                                 out_rows=r1 - r0, raise_flag=raise_flag)
 
     # -- partial-sum multi-GPU (SURVEY §8(e) alternative, §8(f) row 3) -----------------------
     def conv1_partial(self, ws: Workspace, map_classifier: torch.nn.Sequential, out: torch.Tensor,
@@ -780,6 +854,7 @@ class ProjectFuse:
             ops.conv3x3_wino(ws.wino_t, d1, self.pack1w.get(w1), self.mid, init=None, relu=False, out=out,
                              group_mask=gm, tile_order=order, band_rows=band_rows)
             if ws.t_from_warp and ws.guard_src is not None:
+                self._raise_from_params(map_classifier, (ws.nf, ws.nf_tag))
                 self._partial_exact(ws, w1, out, band_rows)
                 ws.guard_src = None  # the frame's produce step ends here
             return out
@@ -835,6 +910,8 @@ class ProjectFuse:
             flag = (ws.nf2, ws.nf2_tag)
         if ws.y1.dtype == torch.float32:
             ops.bias_relu_nonfinite_(ws.y1, init, a1, relu=True, flag=flag)
+            if flag is not None:  # a non-finite w2 / b2 with a finite y1: the exact conv2 all the same
+                self._raise_from_params(map_classifier, flag)
         else:
             ws.y1.add_(init[:, a1:b1]).relu_()
         if mark:
@@ -920,6 +997,17 @@ class ProjectFuse:
 
         ``mark(stage)`` (optional) is called right before each conv is enqueued
         (``bench.py`` records HIP events there)."""
+        if self.nonfinite_guard and ws.t_from_warp and ws.guard_src is not None:
+            # the frame's guard will be armed from the parameters too: while this weight version's scan is open,
+            # the packs and the coord term that run for it anyway look at the weights they read (param_word)
+            self._scan_state = self._param_state(map_classifier)
+            self._scan_state.extra = (("b2", map_classifier[2].bias), ("w3", map_classifier[4].weight))
+        try:
+            return self._fuse(ws, map_classifier, mark)
+        finally:
+            self._scan_state = None
+
+    def _fuse(self, ws: Workspace, map_classifier, mark=None) -> torch.Tensor:
         if self.conv3_fused_applies(ws):
             if mark:
                 mark("conv1")
@@ -929,18 +1017,28 @@ class ProjectFuse:
             self.conv2_partials(ws, map_classifier[2], map_classifier[4])
             if mark:
                 mark("conv3")
-            out = self.conv3_from_partials(ws, map_classifier[4])
-            if ws.t_from_warp and ws.guard_src is not None:
+            guard = ws.t_from_warp and ws.guard_src is not None
+            # a NaN / inf weight takes the exact path too: the raise from the parameters' word rides on the
+            # reduce's launch (no launch of its own per frame)
+            out = self.conv3_from_partials(ws, map_classifier[4], raise_flag=(
+                self.param_word(map_classifier), (ws.nf, ws.nf_tag)) if guard else None)
+            if guard:
                 if mark:
                     mark("guard")
                 self._nonfinite_exact(ws, map_classifier, out, (ws.nf, ws.nf_tag))
                 ws.guard_src = None  # the frame ends here
             return out
-        for stage, idx, fn in (("conv1", 0, self.conv1), ("conv2", 2, self.conv2), ("conv3", 4, self.conv3)):
+        guard = ws.store_y2 and ws.t_from_warp and ws.guard_src is not None
+        for stage, idx, fn in (("conv1", 0, self.conv1), ("conv2", 2, self.conv2)):
             if mark:
                 mark(stage)
-            out = fn(ws, map_classifier[idx])
-        if ws.store_y2 and ws.t_from_warp and ws.guard_src is not None:
+            fn(ws, map_classifier[idx])
+        if mark:
+            mark("conv3")
+        # (the training forward's raise from the parameters' word rides on conv3's launch)
+        out = self.conv3(ws, map_classifier[4], raise_flag=(self.param_word(map_classifier), (ws.nf, ws.nf_tag))
+                         if guard else None)
+        if guard:
             # the training forward (round 6, VERDICT r05 missing 2): the same gated exact path, which also puts
             # its activations where the native backward reads them
             if mark:
@@ -974,8 +1072,9 @@ class ProjectFuse:
 
     def _exact_convs(self, ws: Workspace, map_classifier, out: torch.Tensor, gate, x: torch.Tensor,
                      x_rows: Tuple[int, int], r0: int, r1: int, out_row0: int, packed=None) -> None:
-        """conv1 + coord term + ReLU, conv2 + ReLU and conv3 on the fp32-MFMA kernels (exact products, torch's
-        NaN-preserving ReLU) for map rows [r0, r1), every launch gated on ``gate``: ``x`` is the fp32 slab
+        """conv1 + coord term + ReLU, conv2 + ReLU and conv3 (+ ``:82``'s same-size interpolate, which turns an
+        inf of the map into NaN) on the fp32-MFMA kernels (exact products, torch's NaN-preserving ReLU) for map
+        rows [r0, r1), every launch gated on ``gate``: ``x`` is the fp32 slab
         [S, B, Cs, rows, Wo] holding grid rows ``x_rows``; ``out`` [B, 1, rows, Wo] holds map rows from
         ``out_row0``.  ``packed``: (conv1, conv2) fp32 packs to use (default: the cached ones)."""
         H, W = self.grid_hw
@@ -998,11 +1097,12 @@ class ProjectFuse:
         ops.conv3x3_desc(y1, d2, packed[1], self.mid, bias=c2.bias, dilation=2, relu=True, out=y2, gate=gate)
         if B == 1 or (r0 == out_row0 and r1 - r0 == out.shape[2]):
             ops.conv3x3_cout1(y2, c3.weight, 4, H=H, in_row0=a2, out_row0=r0, out_rows=r1 - r0,
-                              out=out[:, :, r0 - out_row0:r1 - out_row0], gate=gate)
+                              out=out[:, :, r0 - out_row0:r1 - out_row0], gate=gate, same_size_interp=True)
         else:  # a row chunk of B > 1 maps is not contiguous: one launch per item
             for b in range(B):
                 ops.conv3x3_cout1(y2[b:b + 1], c3.weight, 4, H=H, in_row0=a2, out_row0=r0, out_rows=r1 - r0,
-                                  out=out[b:b + 1, :, r0 - out_row0:r1 - out_row0], gate=gate)
+                                  out=out[b:b + 1, :, r0 - out_row0:r1 - out_row0], gate=gate,
+                                  same_size_interp=True)
 
     def _exact_warp_rows(self, ws: Workspace, B: int, s0: int, s1: int, gate) -> torch.Tensor:
         """The reference-order warp (+ upsample) of the frame's views (``ws.guard_src``) into the exact

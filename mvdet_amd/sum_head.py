@@ -20,8 +20,10 @@ fused upsample + warp (``ops.warp_views_adjoint`` with the upsampled ``WarpAdjoi
 gather; the parameter gradients are fixed-order sums.  Everything is fp32 and bitwise repeatable.
 
 Non-finite *geometry* is inside the contract (a pixel whose sample coordinates are not finite for some view
-is NaN, as the reference's warp makes it).  Non-finite *features or weights* are outside it, as for
-``mvbev_warp_views_upsampled``: the commuted order cannot reproduce where the reference's 0 * NaN lands.
+is NaN, as the reference's warp makes it).  Non-finite *features or view weights* are outside it, as for
+``mvbev_warp_views_upsampled``: the commuted order cannot reproduce where the reference's 0 * NaN lands.  A
+non-finite bias, coord weight or ``w2`` with finite features is inside it: every product is formed, and an
+infinite map value is stored as NaN, as ``no_joint_conv_variant.py:81``'s same-size interpolate makes it.
 """
 from __future__ import annotations
 

@@ -15,7 +15,10 @@ sums, no float atomics); the bias and coord-channel gradients come from ``ops.co
 gradient to the planes from ``ops.warp_views_adjoint`` with the plain plans (C = 1).
 
 Non-finite *geometry* is inside the contract (a NaN sample reaches exactly its 3 x 3 neighbourhood in y1, as the
-reference's direct conv makes it).  Non-finite *planes or weights* are outside it, as for ``mvdet_amd.sum_head``.
+reference's direct conv makes it).  So are non-finite conv1 *parameters*: a view is skipped over a tile only when
+its geometry is dead there AND its w1 columns are finite (``ProjectThinFuse.w1_mask``: a device word per weight
+version, read by every block), so y1 keeps the reference's ``0 * NaN = NaN`` pixels.  Non-finite *planes* are
+outside it, as for ``mvdet_amd.sum_head``, and conv2 / conv3 behind y1 are the engine's fast kernels.
 """
 from __future__ import annotations
 
@@ -54,10 +57,22 @@ def _rows(p: torch.Tensor) -> torch.Tensor:
     return p if p.stride(3) == 1 or p.shape[3] == 1 else p.contiguous()
 
 
-def thin_conv1_forward(planes, m_norms, grid_hw, w1, b1, y1: torch.Tensor, xw=None) -> torch.Tensor:
-    """``mvbev_thin_conv1_forward_f32``: ``planes`` N fp32 ``[B,1,H,W]`` tensors with column stride 1, ``m_norms``
+def thin_conv1_weight_mask(w1: torch.Tensor, n_views: int, out=None) -> torch.Tensor:
+    """``mvbev_thin_conv1_weight_mask``: a device int32 word, bit v set when ``w1[:, v]`` holds a NaN / inf."""
+    if not w1.is_contiguous() or w1.dtype != torch.float32 or tuple(w1.shape[1:]) != (n_views + 2, 3, 3):
+        raise ValueError(f"w1 must be a contiguous fp32 [Cout, {n_views + 2}, 3, 3] tensor")
+    if out is None:
+        out = torch.empty(1, dtype=torch.int32, device=w1.device)
+    _native.check(_native.load().mvbev_thin_conv1_weight_mask(w1.data_ptr(), n_views, w1.shape[0], out.data_ptr(),
+                                                              _stream(w1)), "mvbev_thin_conv1_weight_mask")
+    return out
+
+
+def thin_conv1_forward(planes, m_norms, grid_hw, w1, b1, y1: torch.Tensor, xw=None, w_mask=None) -> torch.Tensor:
+    """``mvbev_thin_conv1_forward_f32_ex``: ``planes`` N fp32 ``[B,1,H,W]`` tensors with column stride 1, ``m_norms``
     their kornia matrices (host), ``w1`` ``[Cout,N+2,3,3]``, ``b1`` ``[Cout]`` or None, ``y1`` a contiguous fp32
-    ``[B,Cout,Ho,Wo]`` or split-bf16 (``ops.split_shape``) tensor, ``xw`` None or fp32 ``[B,N,Ho,Wo]``."""
+    ``[B,Cout,Ho,Wo]`` or split-bf16 (``ops.split_shape``) tensor, ``xw`` None or fp32 ``[B,N,Ho,Wo]``, ``w_mask``
+    None (finite weights taken for granted) or ``thin_conv1_weight_mask``'s word for this ``w1``."""
     n = len(planes)
     B, _, H, W = planes[0].shape
     Ho, Wo = int(grid_hw[0]), int(grid_hw[1])
@@ -68,9 +83,12 @@ def thin_conv1_forward(planes, m_norms, grid_hw, w1, b1, y1: torch.Tensor, xw=No
         raise ValueError("w1 and b1 must be contiguous")
     if xw is not None and (tuple(xw.shape) != (B, n, Ho, Wo) or xw.dtype != torch.float32 or not xw.is_contiguous()):
         raise ValueError(f"xw must be a contiguous fp32 {(B, n, Ho, Wo)} tensor")
-    _native.check(_native.load().mvbev_thin_conv1_forward_f32(
+    if w_mask is not None and (w_mask.dtype != torch.int32 or w_mask.numel() < 1 or w_mask.device != y1.device):
+        raise ValueError("w_mask must be an int32 word on y1's device")
+    _native.check(_native.load().mvbev_thin_conv1_forward_f32_ex(
         arr, n, B, H, W, Ho, Wo, w1.data_ptr(), None if b1 is None else b1.data_ptr(), cout, y1.data_ptr(), layout,
-        None if xw is None else xw.data_ptr(), _stream(y1)), "mvbev_thin_conv1_forward_f32")
+        None if xw is None else xw.data_ptr(), None if w_mask is None else w_mask.data_ptr(), _stream(y1)),
+        "mvbev_thin_conv1_forward_f32_ex")
     return y1
 
 
@@ -134,8 +152,9 @@ class ThinFuseFunction(torch.autograd.Function):
         xw = torch.empty((B, n, H, W), dtype=torch.float32, device=dev)
         c1, c2, c3 = _mods(w1.detach(), None if b1 is None else b1.detach(), w2.detach(),
                            None if b2 is None else b2.detach(), w3.detach())
-        thin_conv1_forward([_rows(p.detach()) for p in planes], eng.m_norm_cpu, (H, W), c1.weight.contiguous(),
-                           None if c1.bias is None else c1.bias.contiguous(), y1, xw)
+        w1c = c1.weight.contiguous()
+        thin_conv1_forward([_rows(p.detach()) for p in planes], eng.m_norm_cpu, (H, W), w1c,
+                           None if c1.bias is None else c1.bias.contiguous(), y1, xw, w_mask=head.w1_mask(c1.weight, w1c))
         eng.conv2(ws, c2)
         out = eng.conv3(ws, c3)
         ctx.head, ctx.ws, ctx.xw = head, ws, xw
@@ -198,6 +217,19 @@ class ProjectThinFuse(Rig):
         return self.cached(("plans", dev), lambda: [ops.WarpAdjointPlan(m, self.up_hw, self.grid_hw, dev)
                                                     for m in self.m_norm_cpu])
 
+    def w1_mask(self, w1: torch.Tensor, w1c: torch.Tensor) -> torch.Tensor:
+        """The views whose conv1 columns hold a NaN / inf (``thin_conv1_weight_mask`` of ``w1c``, the contiguous
+        form of ``w1``), once per weight version (keyed on ``w1``'s ``(data_ptr, _version, strides)``, per device;
+        one small launch into a word of the head's, no host sync): the thin kernel evaluates those views over
+        every tile."""
+        st = self.cached(("w1_mask", w1.device), lambda: SimpleNamespace(
+            word=torch.zeros(1, dtype=torch.int32, device=w1.device), key=None))
+        key = (w1.data_ptr(), w1._version, tuple(w1.stride()))
+        if key != st.key:
+            thin_conv1_weight_mask(w1c, self.num_views, st.word)
+            st.key = key
+        return st.word
+
     def __call__(self, planes, w1, b1, w2, b2, w3) -> torch.Tensor:
         """``planes``: one fp32 ``[B,1,H,W]`` tensor per view on one GPU (any batch / channel stride: a channel
         slice of the image result is read in place; a plane whose column stride is not 1 is copied);
@@ -220,8 +252,9 @@ class ProjectThinFuse(Rig):
         ws = eng.workspace(B, dev)
         c1, c2, c3 = _mods(w1.detach(), None if b1 is None else b1.detach(), w2.detach(),
                            None if b2 is None else b2.detach(), w3.detach())
-        thin_conv1_forward([_rows(p.detach()) for p in planes], self.m_norm_cpu, self.grid_hw, c1.weight.contiguous(),
-                           None if c1.bias is None else c1.bias.contiguous(), ws.y1)
+        w1c = c1.weight.contiguous()
+        thin_conv1_forward([_rows(p.detach()) for p in planes], self.m_norm_cpu, self.grid_hw, w1c,
+                           None if c1.bias is None else c1.bias.contiguous(), ws.y1, w_mask=self.w1_mask(c1.weight, w1c))
         if eng.conv3_fused_applies(ws):
             eng.conv2_partials(ws, c2, c3)
             return eng.conv3_from_partials(ws, c3)

@@ -271,6 +271,57 @@ def test_bev_fuse_nonfinite_features_guard():
     assert_parity_t(fine, ref_fine, "bev_fuse finite frame after a non-finite one", normwise_tol=5e-5)
 
 
+@pytest.mark.parametrize("case", ["w1_view_ninf", "b1_pinf"])
+def test_bev_fuse_nonfinite_weights_guard(case):
+    """ABI 12500: ``mvbev_bev_fuse_prepare`` finds a NaN / inf parameter (``plan.params_nonfinite``) and every
+    frame of the plan then takes the exact path — the oracle's pattern for ``w1[5, 64 + 3] = -inf`` at a centre tap
+    (partly finite: the hi/lo split and G w would give all-NaN) and for ``b1[7] = +inf`` (all NaN); prepared again
+    with the finite weights on the same plan and workspace, the fast path's finite map (bitwise the map of a
+    plan that never saw the non-finite weights)."""
+    import nonfinite_weight_cases as nw
+    from mvdet_amd import ops
+    from mvdet_amd.geometry import projection_matrices
+    ds, params = nw.rig()
+    C, N = nw.RIG_C, ds.num_cam
+    up, grid = tuple(ds.upsample_shape), tuple(ds.reducedgrid_shape)
+    pm = projection_matrices(ds)
+    mats = [M.numpy() for M in pm]
+    key, idx, val, kind = nw.CASES[case]
+    feats = nw.features(ds, device=DEV)
+    cpu_feats = [f.cpu() for f in feats]
+
+    def classifier(tp):
+        mc = torch.nn.Sequential(torch.nn.Conv2d(C * N + 2, 512, 3, padding=1), torch.nn.ReLU(),
+                                 torch.nn.Conv2d(512, 512, 3, padding=2, dilation=2), torch.nn.ReLU(),
+                                 torch.nn.Conv2d(512, 1, 3, padding=4, dilation=4, bias=False))
+        mc.load_state_dict({k.replace("map_classifier.", ""): v for k, v in tp.items() if k.startswith("map_classifier.")})
+        return mc.to(DEV)
+
+    tp_fine = {k: torch.from_numpy(v) for k, v in params.items()}
+    tp_bad = nw.poisoned(params, case)
+    bev = ops.BevFuse(_engine_mats(pm, up, grid), C, up, grid)
+    fresh = ops.BevFuse(_engine_mats(pm, up, grid), C, up, grid)
+    with torch.no_grad():
+        bev.prepare(classifier(tp_bad), DEV)
+        assert bev.wino and bev.plan.guard and bev.plan.params_nonfinite == 1
+        got = bev(feats).clone()
+        got2 = bev(feats).clone()  # every frame of the plan, not only the first
+        bev.prepare(classifier(tp_fine), DEV)
+        assert bev.plan.params_nonfinite == 0
+        fine = bev(feats).clone()
+        fresh.prepare(classifier(tp_fine), DEV)
+        assert fresh.plan.params_nonfinite == 0
+        fine_fresh = fresh(feats).clone()
+        torch.cuda.synchronize()
+        ref = cpu_path.project_fuse(cpu_feats, mats, grid, tp_bad)
+        ref_fine = cpu_path.project_fuse(cpu_feats, mats, grid, tp_fine)
+    nw.check_kind(ref, kind)
+    assert_parity_t(got, ref, f"bev_fuse, {case} (NaN / inf pattern included)")
+    assert torch.equal(got.view(torch.int32), got2.view(torch.int32))
+    assert torch.isfinite(fine).all() and torch.equal(fine, fine_fresh)
+    assert_parity_t(fine, ref_fine, "bev_fuse, finite weights prepared after non-finite ones", normwise_tol=5e-5)
+
+
 def test_bev_fuse_guard_in_row_chunks_batch2(monkeypatch):
     """ABI 11900: the one-call guard's exact path in output-row chunks (``MVBEV_BEV_GUARD_BYTES`` small:
     several chunks, each reading its rows +- 7 through a same-size slab window) at B = 2, fp32 sources;

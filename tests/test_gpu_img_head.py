@@ -187,6 +187,31 @@ def test_nonfinite_forward_pattern(layout):
         assert s["n_bad"] == 0 and s["normwise"] <= GATE, s
 
 
+@pytest.mark.parametrize("val", [float("nan"), float("inf"), float("-inf")])
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_nonfinite_weight_meets_an_exact_zero_channel(layout, val):
+    """A non-finite 1x1 weight (a diverging ``optimizer.step()``) on ``test_exact_zero_channel``'s all-zero channel 7
+    of finite features: the reference multiplies 0 * NaN and 0 * inf = NaN at every pixel of that output channel
+    (a kernel that skipped a zero activation would stay finite); on a general channel 12 of output 0, +-inf where
+    the ReLU passes and NaN where it gives 0.  NaN, +inf and -inf patterns equal the fp64 reference's, the finite
+    entries pass the gate."""
+    from mvdet_amd import upsample_relu_conv1x1
+    g = _randn((1, 64, 6, 8), 0)
+    g[:, 7] = 0
+    w = _weight(2, 64, 2)
+    w[1, 7] = val
+    w[0, 12] = val
+    ref = _reference([g], w, (18, 24), check_margin=False)[0][0]
+    assert torch.isnan(ref[0, 1]).all()
+    if val == val:
+        assert 0 < int(torch.isinf(ref[0, 0]).sum()) and 0 < int(torch.isnan(ref[0, 0]).sum()) < ref[0, 0].numel()
+    with torch.no_grad():
+        out = upsample_relu_conv1x1([_to_layout(g, layout)], w.to(DEV), (18, 24))[0].cpu()
+    assert torch.equal(torch.isposinf(out), torch.isposinf(ref)) and torch.equal(torch.isneginf(out), torch.isneginf(ref))
+    s = parity_stats(out, ref)  # asserts the NaN and the non-finite patterns are equal
+    assert s["n_bad"] == 0 and s["normwise"] <= GATE, s
+
+
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_selective_gradients(layout):
     """Case 8: W without grad; g without grad; a loss over views 0 and 2 only.  Wanted gradients match, the

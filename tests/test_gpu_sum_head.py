@@ -177,6 +177,32 @@ def test_degenerate_homography_nan_pattern():
     assert_parity(got["hidden"], torch.relu(ref["pre"]), "degenerate: hidden", normwise_tol=TOL)
 
 
+NONFINITE_PARAMS = [("w2", (2,), float("-inf")), ("w2", (2,), float("nan")), ("bias", (1,), float("-inf")),
+                    ("bias", (1,), float("inf")), ("w_coord", (3, 0), float("inf")), ("w_coord", (3, 1), float("nan"))]
+
+
+@pytest.mark.parametrize("which,idx,val", NONFINITE_PARAMS)
+def test_nonfinite_parameters_forward_pattern(which, idx, val):
+    """A NaN / inf in w2, the bias or a coord weight (a diverging ``optimizer.step()``) with finite features, on the
+    general case's 12 x 17 grid (odd width: the x coord is exactly 0 on the middle column, where 0 * inf = NaN):
+    ``hidden`` and the map have the fp64 reference's NaN, +inf and -inf patterns — w2 = -inf gives -inf where the
+    ReLU passes and NaN where it gives 0, a -inf bias a dead channel and a finite map — and the finite entries
+    pass the gate."""
+    case = Case(3, 2, 5, (7, 9), (20, 31), (12, 17), seed=1)
+    getattr(case, which)[idx] = val
+    got = case.run(layouts=["nchw", "cl", "slice"], grad=())
+    ref = case.reference(backward=False)
+    for name, g, r in (("map", got["map"], ref["map"]), ("hidden", got["hidden"], torch.relu(ref["pre"]))):
+        assert torch.equal(torch.isposinf(g), torch.isposinf(r)), f"{name}: +inf pattern differs"
+        assert torch.equal(torch.isneginf(g), torch.isneginf(r)), f"{name}: -inf pattern differs"
+        assert_parity(g, r, f"{which}{idx} = {val}: {name}", normwise_tol=TOL)  # (NaN pattern included)
+    nf = int((~torch.isfinite(ref["map"])).sum())
+    if which == "bias" and val < 0:
+        assert nf == 0 and torch.count_nonzero(got["hidden"][:, idx[0]]) == 0
+    else:
+        assert nf > 0
+
+
 @pytest.mark.parametrize("subset", ["params", "zs", "one_z_off"])
 def test_needs_input_grad_subsets(subset):
     """Case 5: what needs no gradient gets None, and what does is bitwise what the full backward gave."""

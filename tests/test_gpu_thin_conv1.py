@@ -61,7 +61,8 @@ class Case:
             out.append(t)
         return out
 
-    def forward(self, split=False, want_xw=True, sliced=False):
+    def forward(self, split=False, want_xw=True, sliced=False, mask=False):
+        """``mask``: with the weight word of ``thin_conv1_weight_mask`` (as ``ProjectThinFuse`` calls the kernel)."""
         from mvdet_amd import ops, thin_fuse
         B, (Ho, Wo) = self.B, self.grid
         if split:
@@ -69,8 +70,11 @@ class Case:
         else:
             y1 = torch.full((B, self.cout, Ho, Wo), 7.0, device=DEV)
         xw = torch.full((B, self.N, Ho, Wo), 7.0, device=DEV) if want_xw else None
+        w1 = self.w1.to(DEV)
+        self.mask_word = int(thin_fuse.thin_conv1_weight_mask(w1, self.N).item()) if mask else None
         thin_fuse.thin_conv1_forward(self.gpu_planes(sliced), _m_norms(self.Ms, self.src, self.grid), self.grid,
-                                     self.w1.to(DEV), None if self.b1 is None else self.b1.to(DEV), y1, xw)
+                                     w1, None if self.b1 is None else self.b1.to(DEV), y1, xw,
+                                     w_mask=thin_fuse.thin_conv1_weight_mask(w1, self.N) if mask else None)
         torch.cuda.synchronize()
         y = ops.split_decode(y1, self.cout) if split else y1
         return y.cpu(), None if xw is None else xw.cpu()
@@ -170,6 +174,110 @@ def test_frustum_edge_cases():
     case.planes[0] = case.planes[0] * -3.0 + 7.0  # other data in the view that reaches no pixel
     again, _ = case.forward()
     assert torch.equal(again, y1), "the off-grid view's data changed y1"
+
+
+def _frustum_case():
+    """``test_frustum_edge_cases``'s rig: view 0 entirely off the grid, view 1 covering it, view 2 general."""
+    src, grid = (24, 32), (19, 45)
+    rng = np.random.default_rng(3)
+    off = _rand_h(rng, *src, *grid)
+    off[0, 2] += 1.0e4
+    full = np.diag([grid[1] / src[1] * 1.5, grid[0] / src[0] * 1.5, 1.0])
+    return Case(3, 2, 16, src, grid, seed=3, Ms=[off, full, _rand_h(rng, *src, *grid)])
+
+
+NONFINITE_PARAMS = {
+    # name: (tensor, index, value, bit of the weight word, output channel, what that channel of y1 is)
+    "w1_dead_view_nan": ("w1", (3, 0, 1, 1), float("nan"), 1, 3, "nan"),
+    "w1_dead_view_ninf": ("w1", (3, 0, 1, 1), float("-inf"), 1, 3, "nan"),  # 0 * -inf
+    "w1_general_view_ninf": ("w1", (3, 2, 1, 1), float("-inf"), 4, 3, "mixed"),
+    "b1_ninf": ("b1", (5,), float("-inf"), 0, 5, "zero"),  # a dead channel
+    "w1_coord_x_nan": ("w1", (6, 3, 1, 1), float("nan"), 0, 6, "nan"),
+    "w1_coord_y_pinf": ("w1", (6, 4, 1, 1), float("inf"), 0, 6, "mixed"),  # 0 on the middle row: 0 * inf = NaN
+}
+
+
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("name", sorted(NONFINITE_PARAMS))
+def test_nonfinite_conv1_parameters(name, split):
+    """A NaN / inf at a centre tap of w1 (a view entirely off the grid, whose tiles the kernel skips when its
+    weights are finite: the reference multiplies 0 * NaN = NaN at every pixel; a general view; a coord channel, on
+    a grid with odd sides whose coord value is exactly 0 on the middle row / column) or in b1: y1's NaN / inf
+    pattern is the fp64 reference's, fp32 layout and split-bf16 (which keeps NaN and the finite values; its
+    hi / lo pair of +inf decodes as NaN, so there the non-finite entries are compared as such), the other
+    channels untouched.  The weight word marks exactly the views whose w1 columns are non-finite."""
+    case = _frustum_case()
+    base, _ = case.forward(split=split, mask=True)
+    assert case.mask_word == 0
+    plain, _ = case.forward(split=split)
+    assert torch.equal(base, plain), "finite weights: the weight word must not change y1"
+    which, idx, val, bit, co, kind = NONFINITE_PARAMS[name]
+    getattr(case, which)[idx] = val
+    ref = case.reference()["y1"]
+    y1, _ = case.forward(split=split, mask=True)
+    assert case.mask_word == bit
+    r = ref[:, co]
+    if kind == "nan":
+        assert torch.isnan(r).all()
+    elif kind == "zero":
+        assert torch.count_nonzero(r) == 0
+    else:
+        assert 0 < int(torch.isnan(r).sum()) < r.numel() and int(torch.isposinf(r).sum()) > 0
+    others = [c for c in range(case.cout) if c != co]
+    assert torch.isfinite(ref[:, others]).all() and torch.equal(y1[:, others], base[:, others])
+    assert torch.equal(~torch.isfinite(y1), ~torch.isfinite(ref)), "non-finite pattern differs"
+    if split:
+        assert torch.isnan(y1[torch.isnan(ref)]).all()
+        fin = torch.isfinite(ref)
+        assert_parity(y1[fin], ref[fin], f"{name}: finite entries of y1 (split)", normwise_tol=TOL)
+    else:
+        assert torch.equal(torch.isposinf(y1), torch.isposinf(ref)) and not torch.isneginf(y1).any()
+        assert_parity(y1, ref, f"{name}: y1", normwise_tol=TOL)
+
+
+@pytest.mark.parametrize("train", [False, True])
+def test_head_weight_word_follows_w1_in_place(train):
+    """``ProjectThinFuse`` itself (inference, and the training forward of ``ThinFuseFunction``): its cached weight
+    word (``w1_mask``, keyed on w1's ``(data_ptr, _version, strides)``) follows w1 poisoned and restored IN PLACE —
+    finite: word 0; ``w1[3, 0] = NaN`` at the centre tap of the off-grid view: bit 0, and (inference) channel 3 of
+    the head's y1 all NaN as the reference's; restored: word 0 again and y1 bitwise the first one."""
+    from mvdet_amd import ProjectThinFuse, ops
+    case = _frustum_case()
+    mid = 128
+    rng = np.random.default_rng(7)
+    k = 1.0 / np.sqrt(9 * (case.N + 2))
+    w1 = torch.from_numpy(rng.uniform(-k, k, (mid, case.N + 2, 3, 3)).astype(np.float32)).to(DEV)
+    b1 = torch.from_numpy(rng.uniform(-k, k, mid).astype(np.float32)).to(DEV)
+    w2 = torch.from_numpy((rng.uniform(-1, 1, (mid, mid, 3, 3)) / np.sqrt(9 * mid)).astype(np.float32)).to(DEV)
+    b2 = torch.zeros(mid, device=DEV)
+    w3 = torch.from_numpy((rng.uniform(-1, 1, (1, mid, 3, 3)) / np.sqrt(9 * mid)).astype(np.float32)).to(DEV)
+    if train:
+        w1.requires_grad_()
+    head = ProjectThinFuse([torch.from_numpy(np.asarray(M)) for M in case.Ms], case.src, case.grid, mid_channels=mid)
+    planes = case.gpu_planes()
+
+    def run():
+        out = head(planes, w1, b1, w2, b2, w3)
+        assert (out.grad_fn is not None) == train
+        word = int(head.w1_mask(w1.detach(), w1.detach()).item())
+        y1 = None if train else ops.split_decode(head.engine.workspace(case.B, DEV).y1, mid).clone()
+        return word, y1, out.detach().clone()
+
+    word0, y0, out0 = run()
+    assert word0 == 0 and torch.isfinite(out0).all()
+    with torch.no_grad():
+        old = w1[3, 0, 1, 1].item()
+        w1[3, 0, 1, 1] = float("nan")
+    word1, y1, _ = run()
+    assert word1 == 1
+    if not train:
+        assert torch.isnan(y1[:, 3]).all() and torch.isfinite(y1[:, :3]).all() and torch.isfinite(y1[:, 4:]).all()
+    with torch.no_grad():
+        w1[3, 0, 1, 1] = old
+    word2, y2, out2 = run()
+    assert word2 == 0 and torch.equal(out2, out0)
+    if not train:
+        assert torch.equal(y2, y0)
 
 
 @pytest.mark.parametrize("grid", [(1, 37), (19, 1)])

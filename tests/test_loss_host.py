@@ -204,4 +204,4 @@ def test_public_surface():
     for name in ("mvbev_adaptive_max_pool_f32", "mvbev_gaussian_mse_f32", "mvbev_loss_finalize_f32",
                  "mvbev_gaussian_mse_backward_f32"):
         assert name in _native.EXPORTS
-    assert _native.load().mvbev_version() == 12400
+    assert _native.load().mvbev_version() == 12500

@@ -214,3 +214,50 @@ def test_masked_relu_is_torch_relu_nan_included(n):
     nan = torch.isnan(pre)
     assert nan.any() and torch.equal(b.grad[nan], grad[nan])  # torch passes the gradient at a NaN
     assert torch.equal(b.grad, torch.ops.aten.threshold_backward(grad, yb.detach(), 0))
+
+
+def test_nonfinite_weight_cases_discriminate():
+    """The oracle maps of ``nonfinite_weight_cases.CASES`` (one NaN / inf at a centre tap of a ``map_classifier``
+    parameter) are what the table says: the "partial" rows partly finite (a fast path that turns inf into NaN
+    gives all-NaN there), the -inf bias rows wholly finite (a dead channel), the rest all NaN — so the GPU cases
+    of ``test_gpu_nonfinite_weights.py`` cannot silently become trivial if the fixtures change.  The view-1 w1
+    cases also need a conv1 tile that view 1's frustum leaves out (where the fast path's mask never multiplies
+    the weight): the last tile column, 8 grid columns past the warped view's footprint."""
+    import nonfinite_weight_cases as nw
+    from mvdet_amd.geometry import projection_matrices
+    ds, params = nw.rig()
+    grid = tuple(ds.reducedgrid_shape)
+    assert (ds.num_cam, tuple(ds.upsample_shape), grid) == (3, (54, 96), (24, 72))
+    pm = [M.numpy() for M in projection_matrices(ds)]
+    feats = nw.features(ds)
+    with torch.no_grad():
+        base = cpu_path.project_fuse(feats, pm, grid, {k: torch.from_numpy(v) for k, v in params.items()})
+        assert torch.isfinite(base).all()
+        kinds = set()
+        for name, (_, _, _, kind) in nw.CASES.items():
+            ref = cpu_path.project_fuse(feats, pm, grid, nw.poisoned(params, name))
+            nw.check_kind(ref, kind)
+            kinds.add(kind)
+        assert kinds == {"nan", "partial", "finite"}
+        warped1 = cpu_path.warp_views([torch.ones(1, 1, *ds.upsample_shape)] * 3, pm, grid)[1][0, 0]
+    cols = torch.nonzero(warped1.ne(0).any(0)).flatten()
+    assert int(cols.max()) + 1 < 64 - 1  # view 1 is exactly zero over the tile column [64, 72) and its halo
+
+
+def test_same_size_interpolate_turns_inf_into_nan_and_nothing_else():
+    """``persp_trans_detector.py:82``'s ``F.interpolate`` of the map to its own size (the oracle's last step) is
+    the identity bit for bit on finite values and keeps NaN, but turns +-inf into NaN at that pixel (torch's lerp
+    ``x + 0 * (x' - x)``): the rule the exact path's conv3 applies (``MVBEV_COUT1_SAME_SIZE_INTERP``), pinned here
+    at the test grid, an odd one and config 2's."""
+    g = torch.Generator().manual_seed(0)
+    for shape in [(1, 1, 24, 72), (2, 1, 9, 71), (1, 1, 120, 360)]:
+        x = torch.randn(shape, generator=g)
+        m = torch.rand(shape, generator=g)
+        x[m < 0.05] = float("inf")
+        x[(m >= 0.05) & (m < 0.1)] = float("-inf")
+        x[(m >= 0.1) & (m < 0.15)] = float("nan")
+        x[..., 0, 0], x[..., -1, -1], x[..., -1, 0] = float("inf"), float("-inf"), float("inf")
+        y = F.interpolate(x, list(shape[2:]), mode="bilinear")
+        assert not torch.isinf(y).any() and torch.equal(torch.isnan(y), ~torch.isfinite(x))
+        fin = torch.isfinite(x)
+        assert torch.equal(y[fin].view(torch.int32), x[fin].view(torch.int32))

@@ -94,7 +94,7 @@ def test_entry_points_are_exported_and_the_version_stays():
                          check=True).stdout
     for n in NAMES:
         assert f" T {n}\n" in out, n
-    assert _native.load().mvbev_version() == 12400
+    assert _native.load().mvbev_version() == 12500
 
 
 def _views(n=1, src=P, colstride=1, stride=32):

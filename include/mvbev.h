@@ -1065,6 +1065,43 @@ int mvbev_thin_conv1_backward_f32(const float* dpre, const float* w1, const floa
 int mvbev_thin_conv1_grad_weight_f32(const float* partials, int64_t nblocks, int nviews, int64_t Cout, float* dw,
                                      void* stream);
 
+/* ---- the front and the closing upsample of ImageProjVariant (added after 12500; mvbev_version() stays 12500) ----
+ *
+ * image_proj_variant.py:64-88 in one launch: per view F.interpolate(imgs[:, cam], upsample_shape, 'bilinear')
+ * (:67), kornia.warp_perspective(img_res, proj_mat, reducedgrid_shape) (:69), and the torch.cat of the N warped
+ * 3-channel maps with the coord map (:88):
+ *   out[b][3 v + c][r][u]            = the kornia warp (mvbev_warp_perspective_f32's coordinates, blend and zero
+ *                                      padding; non-finite coordinates give NaN) of the RESIZED image [Hr][Wr] of
+ *                                      view v's channel c, each in-bounds corner of which is PyTorch's
+ *                                      align_corners=False bilinear resize of the full-resolution [H][W] image
+ *                                      (source index scale (dst + 0.5) - 0.5 clamped at 0 with scale = in / out in
+ *                                      fp32, the second tap clamped at the edge): at most 16 taps per sample
+ *   out[b][3 N], out[b][3 N + 1]     = the coord values of mvbev_fill_coord_map_f32
+ * The resized images are never written.  views[i]: src = view i's image [B][3][H][W] fp32 at element strides
+ * src_strides (batch, channel and row strides >= 0, column stride 1: a slice imgs[:, i] of a [B][N][3][H][W] tensor
+ * runs without a copy), m = the kornia matrix for a source of Hr x Wr; dst unused.  out: [B][3 N + 2][Ho][Wo] fp32
+ * at element strides out_strides (>= 0; NCHW and channels-last outputs hold bitwise-equal values).  flags: 0, or
+ * MVBEV_IMG_PROJ_PER_PIXEL (one thread per grid pixel walks the views, instead of one thread per (pixel, view);
+ * the same values).  NaN / Inf in the images are outside the contract (an invalid corner is not multiplied).
+ * Range: 1 <= nviews <= 16, every tensor below 2^31 elements (else MVBEV_ERR_SHAPE, as an unknown flag; a size <= 0
+ * is MVBEV_ERR_RANK, a column stride != 1 or a negative stride MVBEV_ERR_STRIDE, a missing pointer
+ * MVBEV_ERR_NULL). */
+#define MVBEV_IMG_PROJ_PER_PIXEL 1
+int mvbev_img_proj_forward_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t H, int64_t W, int64_t Hr,
+                               int64_t Wr, int64_t Ho, int64_t Wo, float* out, const int64_t out_strides[4], int flags,
+                               void* stream);
+
+/* image_proj_variant.py:92, F.interpolate(map_result, reducedgrid_shape, mode='bilinear') of a one-channel map:
+ * x [B][1][h][w] -> y [B][1][Ho][Wo], both fp32 contiguous, PyTorch's align_corners=False taps and order.  Any
+ * ratio >= 1 per axis (Ho >= h, Wo >= w; else MVBEV_ERR_SHAPE), integer or not. */
+int mvbev_upsample_map_f32(const float* x, int64_t B, int64_t h, int64_t w, int64_t Ho, int64_t Wo, float* y,
+                           void* stream);
+/* Its adjoint: dx[b][i][j] = the sum over the output pixels whose taps touch (i, j) of weight * dy, gathered per
+ * low-resolution pixel in a fixed order (no float atomics: bitwise repeatable).  dy [B][1][Ho][Wo], dx [B][1][h][w],
+ * fp32 contiguous; every dx value is written. */
+int mvbev_upsample_map_backward_f32(const float* dy, int64_t B, int64_t h, int64_t w, int64_t Ho, int64_t Wo,
+                                    float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,10 @@ Public surface (mirrors the reference's):
   (``mvdet_amd.variants``); ``ProjectThinFuse`` — its ground-plane head: warp of the views' foot planes, coord
   channels, the thin first conv, bias and ReLU as one launch, then the engine's conv2 / conv3, with a native
   backward (``mvdet_amd.thin_fuse``).
+* ``ImageProjVariant`` — drop-in for ``multiview_detector.models.image_proj_variant.ImageProjVariant``
+  (``mvdet_amd.variants``); ``ImageProjection`` — its front: image resize, warp, concat and coord channels as one
+  launch (``mvdet_amd.img_proj``); ``DenseFuseHead`` — its ground-plane head on the dense world feature: the three
+  convs and the closing bilinear upsample, with a native backward (``mvdet_amd.dense_head``).
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -36,8 +40,13 @@ from . import sum_head  # noqa: F401
 from .sum_head import ProjectSumHead  # noqa: F401
 from . import thin_fuse  # noqa: F401
 from .thin_fuse import ProjectThinFuse  # noqa: F401
-from .variants import NoJointConvVariant, ResProjVariant  # noqa: F401
+from . import img_proj  # noqa: F401
+from .img_proj import ImageProjection  # noqa: F401
+from . import dense_head  # noqa: F401
+from .dense_head import DenseFuseHead  # noqa: F401
+from .variants import ImageProjVariant, NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
            "detection_loss", "gaussian_kernels", "img_head", "upsample_relu_conv1x1",
-           "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant"]
+           "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant",
+           "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant"]

@@ -132,7 +132,12 @@ EXPORTS = (
     "mvbev_mask_gated_u32",
     "mvbev_pack_conv3x3_weight_wino_ex",
     "mvbev_coord_term_f32_ex",
+    # the front and the closing upsample of ImageProjVariant (added after 12500; the version stays 12500)
+    "mvbev_img_proj_forward_f32",
+    "mvbev_upsample_map_f32",
+    "mvbev_upsample_map_backward_f32",
 )
+IMG_PROJ_PER_PIXEL = 1  # MVBEV_IMG_PROJ_PER_PIXEL
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
 BEV_SRC_CHANNELS_LAST = 16  # MVBEV_BEV_SRC_CHANNELS_LAST (flag)
 BEV_NO_GUARD = 32  # MVBEV_BEV_NO_GUARD (flag, ABI 11900)
@@ -507,6 +512,13 @@ def _declare(lib):
     lib.mvbev_thin_conv1_backward_f32.argtypes = [_p, _p, _p, ctypes.c_int, _i64, _i64, _i64, _i64, _p, _p, _i64, _p]
     lib.mvbev_thin_conv1_grad_weight_f32.restype = ctypes.c_int
     lib.mvbev_thin_conv1_grad_weight_f32.argtypes = [_p, _i64, ctypes.c_int, _i64, _p, _p]
+    lib.mvbev_img_proj_forward_f32.restype = ctypes.c_int
+    lib.mvbev_img_proj_forward_f32.argtypes = ([ctypes.POINTER(WarpView), ctypes.c_int] + [_i64] * 7 +
+                                               [_p, _i64x4, ctypes.c_int, _p])  # out, out_strides, flags, stream
+    for name in ("mvbev_upsample_map_f32", "mvbev_upsample_map_backward_f32"):
+        fn = getattr(lib, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [_p] + [_i64] * 5 + [_p, _p]
 
 
 def load(path: os.PathLike | str | None = None):

@@ -42,9 +42,10 @@ class BasicBlock(nn.Module):
         return self.relu(out + identity)
 
 
-def resnet18_trunk(replace_stride_with_dilation=(False, True, True)) -> nn.Sequential:
-    """ResNet-18 without avgpool/fc: children conv1, bn1, relu, maxpool, layer1-4."""
-    mods: List[nn.Module] = [nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
+def resnet18_trunk(replace_stride_with_dilation=(False, True, True), in_channels: int = 3) -> nn.Sequential:
+    """ResNet-18 without avgpool/fc: children conv1, bn1, relu, maxpool, layer1-4.  ``in_channels``: of conv1
+    (``resnet.py:121,138``; ``image_proj_variant.py:44-45`` builds it with ``3 * num_cam + 2``)."""
+    mods: List[nn.Module] = [nn.Conv2d(in_channels, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
                              nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1)]
     cin, dilation = 64, 1
     for planes, stride, dilate in ((64, 1, False), (128, 2, replace_stride_with_dilation[0]),
@@ -68,10 +69,10 @@ def resnet18_trunk(replace_stride_with_dilation=(False, True, True)) -> nn.Seque
     return trunk
 
 
-def vgg11_features() -> nn.Sequential:
-    """torchvision ``vgg11().features`` layout (indices 0..20)."""
+def vgg11_features(in_channels: int = 3) -> nn.Sequential:
+    """torchvision ``vgg11().features`` layout (indices 0..20); ``in_channels``: of the first conv."""
     layers: List[nn.Module] = []
-    cin = 3
+    cin = in_channels
     for v in (64, "M", 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M"):
         if v == "M":
             layers.append(nn.MaxPool2d(2, 2))
@@ -84,15 +85,16 @@ def vgg11_features() -> nn.Sequential:
     return nn.Sequential(*layers)
 
 
-def build_backbone(arch: str) -> Tuple[nn.Sequential, nn.Sequential, int]:
-    """(base_pt1, base_pt2, out_channel) as ``persp_trans_detector.py:32-47``."""
+def build_backbone(arch: str, in_channels: int = 3) -> Tuple[nn.Sequential, nn.Sequential, int]:
+    """(base_pt1, base_pt2, out_channel) as ``persp_trans_detector.py:32-47``; ``in_channels``: of the first conv
+    (``image_proj_variant.py:35-49``: the ground-plane backbone's ``3 * num_cam + 2``)."""
     if arch == "vgg11":
-        base = vgg11_features()
+        base = vgg11_features(in_channels)
         base[-1] = nn.Sequential()
         base[-4] = nn.Sequential()
         split = 10
     elif arch == "resnet18":
-        base = resnet18_trunk((False, True, True))
+        base = resnet18_trunk((False, True, True), in_channels)
         split = 7
     else:
         raise Exception("architecture currently support [vgg11, resnet18]")

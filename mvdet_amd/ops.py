@@ -1341,6 +1341,56 @@ def cout1_from_partials(partials: torch.Tensor, desc, cout: int, dilation3: int,
     return out
 
 
+def _check_map_resize(small: torch.Tensor, size, what: str):
+    """The checks of ``upsample_map`` / ``upsample_map_backward``: ``small`` fp32 [B,1,h,w], ``size`` = (Ho, Wo) with
+    a ratio >= 1 per axis."""
+    if small.dim() != 4 or small.shape[1] != 1 or small.dtype != torch.float32:
+        raise ValueError(f"{what} must be a float32 [B,1,h,w] map, got {small.dtype} {tuple(small.shape)}")
+    if len(size) != 2:
+        raise ValueError(f"size must be (rows, columns), got {size!r}")
+    Ho, Wo = int(size[0]), int(size[1])
+    if Ho < small.shape[2] or Wo < small.shape[3]:
+        raise ValueError(f"upsample_map resizes by a ratio >= 1 per axis: {tuple(small.shape[2:])} -> {(Ho, Wo)}")
+    return Ho, Wo
+
+
+def upsample_map(x: torch.Tensor, size) -> torch.Tensor:
+    """``F.interpolate(x, size, mode='bilinear')`` (``align_corners=False``) of a one-channel fp32 map ``[B,1,h,w]``
+    -> ``[B,1,Ho,Wo]`` (``mvbev_upsample_map_f32``; ``image_proj_variant.py:92``), any ratio >= 1 per axis.  Equal
+    sizes return ``x`` itself: the elided identity, as the other models' closing interpolate."""
+    Ho, Wo = _check_map_resize(x, size, "x")
+    B, _, h, w = x.shape
+    if (Ho, Wo) == (h, w):
+        return x
+    _require_cuda(x)
+    x = x.contiguous()
+    y = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=x.device)
+    st = _native.load().mvbev_upsample_map_f32(x.data_ptr(), B, h, w, Ho, Wo, y.data_ptr(), _stream(x))
+    _native.check(st, "mvbev_upsample_map_f32")
+    return y
+
+
+def upsample_map_backward(dy: torch.Tensor, hw) -> torch.Tensor:
+    """The adjoint of ``upsample_map``: ``dy`` fp32 ``[B,1,Ho,Wo]`` -> ``[B,1,h,w]`` for ``hw = (h, w)``, a fixed-order
+    gather per low-resolution pixel (``mvbev_upsample_map_backward_f32``: no float atomics).  Equal sizes return
+    ``dy`` itself."""
+    if dy.dim() != 4 or dy.shape[1] != 1 or dy.dtype != torch.float32 or len(hw) != 2:
+        raise ValueError(f"dy must be a float32 [B,1,Ho,Wo] map and hw (rows, columns), got {dy.dtype} "
+                         f"{tuple(dy.shape)} and {hw!r}")
+    B, _, Ho, Wo = dy.shape
+    h, w = int(hw[0]), int(hw[1])
+    if h <= 0 or w <= 0 or Ho < h or Wo < w:
+        raise ValueError(f"upsample_map resizes by a ratio >= 1 per axis: {(h, w)} -> {(Ho, Wo)}")
+    if (Ho, Wo) == (h, w):
+        return dy
+    _require_cuda(dy)
+    dy = dy.contiguous()
+    dx = torch.empty((B, 1, h, w), dtype=torch.float32, device=dy.device)
+    st = _native.load().mvbev_upsample_map_backward_f32(dy.data_ptr(), B, h, w, Ho, Wo, dx.data_ptr(), _stream(dy))
+    _native.check(st, "mvbev_upsample_map_backward_f32")
+    return dx
+
+
 # ----------------------------------------------------------------------------------------------
 # backward (SURVEY §8(f) row 2): the adjoints autograd needs to train through the hot path
 

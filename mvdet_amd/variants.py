@@ -21,13 +21,32 @@ coord map, and ``map_classifier`` is ``PerspTransDetector``'s three 3x3 convs ov
 warp + coord channels + conv1 + bias + ReLU are one HIP launch and conv2 / conv3 the engine's
 (``mvdet_amd.thin_fuse.ProjectThinFuse``), in inference and under autograd, where the planes' gradient joins the
 loss's own gradient of ``imgs_result`` on its way into the image head's backward.
+
+``ImageProjVariant`` (``multiview_detector/models/image_proj_variant.py:16-118``) is the "early fusion" ablation: the
+3-channel IMAGES are resized (``:67``), warped (``:69``) and concatenated with the coord map (``:88``), ONE ResNet-18
+with ``3 * num_cam + 2`` input channels runs on the ground plane (``:44-48,89-90``), and ``map_classifier`` is three
+3x3 convs without coord channels on the dense ``[B,512,h',w']`` world feature at 1/8 of the grid (``:53-56,91``),
+followed by a real ~8x bilinear interpolate (``:92``).  Same drop-in contract (no ``img_classifier``: the
+``state_dict`` holds ``base_pt1.*``, ``base_pt2.*``, ``map_classifier.{0,2,4}.*``; ``imgs_result`` is N all-zero
+``[B,2,H,W]`` tensors at the input image size, ``:65-66``).  The backbone is torch; everything in front of it is one
+HIP launch (``mvdet_amd.img_proj``: resize + warp + concat + coord channels, born in the backbone's memory format)
+and everything behind it the native dense head (``mvdet_amd.dense_head``: the MFMA convs and the closing upsample,
+in inference and under autograd); ``native_map_head=False`` keeps ``map_classifier`` + ``F.interpolate`` as torch
+ops, the front stays native.  Nothing in front of the backbone has parameters, so the front has no backward.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
+from . import _native
+from .backbone import build_backbone
+from .dense_head import DenseFuseHead
 from .detector import _ViewsDetector
+from .geometry import coord_map as make_coord_map
+from .geometry import projection_matrices, upsample_shape
+from .img_proj import ImageProjection
 from .sum_head import ProjectSumHead
 from .thin_fuse import ProjectThinFuse
 
@@ -95,4 +114,52 @@ class ResProjVariant(_ViewsDetector):
             for r in imgs_result:
                 self._show(r[0, 0].detach())
             self._show(torch.norm(map_result[0].detach(), dim=0))
+        return map_result, imgs_result
+
+
+class ImageProjVariant(_ViewsDetector):
+    def __init__(self, dataset, arch: str = "resnet18", device=None, channels_last: bool = True,
+                 native_map_head: bool = True):
+        super().__init__()
+        self.num_cam = dataset.num_cam
+        self.img_shape, self.reducedgrid_shape = list(dataset.img_shape), list(dataset.reducedgrid_shape)
+        self.coord_map = make_coord_map(*self.reducedgrid_shape)                    # :24 (not a buffer)
+        self.upsample_shape = upsample_shape(self.img_shape, dataset.img_reduce)   # :26
+        self.proj_mats = projection_matrices(dataset)                               # :21-33 (fp64 list)
+        if device is None:
+            device = "cuda:0" if torch.cuda.is_available() else "cpu"
+        self._device = torch.device(device)
+        if self._device.type == "cuda":
+            _native.load()  # no fallback: fail at construction if the HIP library is missing
+        self.base_pt1, self.base_pt2, out_channel = build_backbone(arch, in_channels=3 * self.num_cam + 2)  # :35-49
+        self.map_classifier = nn.Sequential(nn.Conv2d(out_channel, 512, 3, padding=1), nn.ReLU(),
+                                            nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),
+                                            nn.Conv2d(512, 1, 3, padding=4, dilation=4, bias=False))  # :53-56
+        self.channels_last = bool(channels_last)
+        # on: map_classifier and the closing interpolate on the HIP kernels (dense_head.py), inference and training;
+        # off: the torch ops (the front is native either way)
+        self.native_map_head = bool(native_map_head)
+        self._place()
+        self.front = ImageProjection(self.proj_mats, tuple(self.upsample_shape), tuple(self.reducedgrid_shape))
+        self.head = DenseFuseHead(tuple(self.reducedgrid_shape))
+
+    def forward(self, imgs: torch.Tensor, visualize: bool = False):
+        B, N, C, H, W = imgs.shape
+        assert N == self.num_cam
+        dev = self._device
+        if dev.type != "cuda":
+            raise RuntimeError("ImageProjVariant.forward needs a ROCm GPU (the hot path has no CPU fallback)")
+        imgs = imgs.to(dev)  # once, not per camera (:67)
+        # one memset where the reference has N (:65-66)
+        imgs_result = list(torch.zeros([N, B, 2, H, W], device=dev).unbind(0))
+        projected_imgs = self.front(imgs, channels_last=self.channels_last)          # :67-69, :88
+        if visualize:
+            for cam in range(N):
+                self._show(projected_imgs[0, 3 * cam:3 * cam + 3].detach().permute(1, 2, 0))
+        world_feature = self.base_pt2(self.base_pt1(projected_imgs))                  # :89-90
+        if self.native_map_head:
+            c1, c2, c3 = self.map_classifier[0], self.map_classifier[2], self.map_classifier[4]
+            map_result = self.head(world_feature, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight)  # :91-92
+        else:
+            map_result = F.interpolate(self.map_classifier(world_feature), self.reducedgrid_shape, mode="bilinear")
         return map_result, imgs_result

@@ -123,3 +123,16 @@ def load_reference_res_proj_variant():
     matplotlib.use("Agg")
     from multiview_detector.models.res_proj_variant import ResProjVariant
     return ResProjVariant
+
+
+def load_reference_image_proj_variant():
+    """The reference's ``ImageProjVariant`` (``tools/gen_golden_img_proj.py``).  Its file imports the torchvision
+    submodules ``load_reference_res_proj_variant`` stubs, and ``cv2`` (only named in commented-out lines): an empty
+    placeholder module stands in where OpenCV is not installed."""
+    load_reference_res_proj_variant()  # (the kornia / torchvision stubs and the path)
+    try:
+        import cv2  # noqa: F401
+    except ImportError:
+        sys.modules["cv2"] = types.ModuleType("cv2")
+    from multiview_detector.models.image_proj_variant import ImageProjVariant
+    return ImageProjVariant

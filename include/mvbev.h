@@ -895,6 +895,35 @@ int mvbev_gaussian_mse_f32(const mvbev_loss_item* items, int n, int64_t B, const
                            int nkernels, float cls_thres, int stats_item, double* partials, int64_t npartials,
                            void* stream);
 
+/* Point-list targets.  Added after 12400 (mvbev_version() stays): mvbev_loss_points,
+ * mvbev_gaussian_mse_points_f32.  A record parallel to items[i] that holds the non-zero cells of
+ * the item's logical [B][C][Ht][Wt] target instead of the dense tensor: the item's target and pooled
+ * are then unused (may be NULL) and no pooling launch is needed for it.  All three pointers NULL: a
+ * dense item, handled as by mvbev_gaussian_mse_f32. */
+typedef struct mvbev_loss_points {
+  const int32_t* cells;    /* device [n][3]: channel, row, column of each cell, every (b, c, row, col) at most
+                            * once, sorted by batch item; 0 <= channel < C, 0 <= row < Ht, 0 <= column < Wt */
+  const float* values;     /* device [n]: the cells' values, finite and >= 0 (ground truth is counts) */
+  const int32_t* offsets;  /* device [B + 1]: batch item b owns cells offsets[b] .. offsets[b + 1] - 1 */
+  int64_t Ht, Wt;          /* must equal items[i].Ht, items[i].Wt */
+} mvbev_loss_points;
+
+/* mvbev_gaussian_mse_f32 with a record per item (points: host array of n).  For a point item the
+ * workgroup zero-fills its LDS tile and raises, for every cell (c, r, q, value) of its batch item, the
+ * pooled cells rows floor(r h / Ht) .. ceil((r + 1) h / Ht) - 1, columns floor(q w / Wt) ..
+ * ceil((q + 1) w / Wt) - 1 (those whose adaptive_max_pool2d window holds the cell), clipped to the tile
+ * plus halo, to the value with an integer maximum: the staged tile, and so every output, is bitwise
+ * what mvbev_adaptive_max_pool_f32 + mvbev_gaussian_mse_f32 give on the dense tensor of the same cells.
+ * The cell lists are the caller's contract (they live on the device and are not read here); a channel
+ * out of range or a value <= 0 is skipped by the kernel, a row or column out of range is clipped.
+ * Same return codes as mvbev_gaussian_mse_f32, plus MVBEV_ERR_NULL for points == NULL or a record
+ * with some but not all of its pointers, and MVBEV_ERR_SHAPE for a record whose Ht, Wt are not the
+ * item's (or exceed 2^31 - 1).  mvbev_gaussian_mse_blocks, the partials, finalize and the backward
+ * serve both kinds of item unchanged. */
+int mvbev_gaussian_mse_points_f32(const mvbev_loss_item* items, const mvbev_loss_points* points, int n,
+                                  int64_t B, const mvbev_loss_kernel* kernels, int nkernels, float cls_thres,
+                                  int stats_item, double* partials, int64_t npartials, void* stream);
+
 /* Sums the partials in a fixed order in fp64: *loss = sum_i weight_i sse_i / (B C_i h_i w_i)
  * (fp32); stats (optional, fp64[3]) = tp, fp = pred - tp, fn = gt_sum - tp of item stats_item. */
 int mvbev_loss_finalize_f32(const mvbev_loss_item* items, int n, int64_t B, const double* partials,

@@ -11,6 +11,9 @@ Public surface (mirrors the reference's):
 * ``GaussianMSE`` / ``detection_loss`` / ``gaussian_kernels`` — drop-ins for
   ``multiview_detector.loss.gaussian_mse.GaussianMSE`` and the loss / precision-recall lines of
   ``trainer.py:43-56`` (``mvdet_amd.loss``).
+* ``PointTargets`` / ``pack_step`` — the ground truth as point lists from the dataset's ``coo_matrix``
+  objects to the criterion's kernel, one upload of a few kB per step (``mvdet_amd.targets``); the
+  criterion takes one wherever it takes a dense target, with bitwise the dense result.
 * ``upsample_relu_conv1x1`` — the image head after its first conv (bilinear upsample, ReLU, 1x1
   conv) for all views in one launch, with a native backward (``mvdet_amd.img_head``).
 * ``NoJointConvVariant`` — drop-in for ``multiview_detector.models.no_joint_conv_variant.NoJointConvVariant``
@@ -34,6 +37,8 @@ from .pipeline import ProjectFuse  # noqa: F401
 from . import postprocess  # noqa: F401
 from . import loss  # noqa: F401
 from .loss import GaussianMSE, detection_loss, gaussian_kernels  # noqa: F401
+from . import targets  # noqa: F401
+from .targets import PointTargets, pack_step  # noqa: F401
 from . import img_head  # noqa: F401
 from .img_head import upsample_relu_conv1x1  # noqa: F401
 from . import sum_head  # noqa: F401
@@ -47,6 +52,6 @@ from .dense_head import DenseFuseHead  # noqa: F401
 from .variants import ImageProjVariant, NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
-           "detection_loss", "gaussian_kernels", "img_head", "upsample_relu_conv1x1",
+           "detection_loss", "gaussian_kernels", "targets", "PointTargets", "pack_step", "img_head", "upsample_relu_conv1x1",
            "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant",
            "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant"]

@@ -106,6 +106,7 @@ EXPORTS = (
     "mvbev_gaussian_mse_f32",
     "mvbev_loss_finalize_f32",
     "mvbev_gaussian_mse_backward_f32",
+    "mvbev_gaussian_mse_points_f32",  # point-list targets (mvdet_amd.targets)
     # the fused image head (added after 12400; the version stays 12400)
     "mvbev_img_head_forward_f32",
     "mvbev_img_head_backward_blocks",
@@ -216,6 +217,12 @@ class LossKernel(ctypes.Structure):
     """``mvbev_loss_kernel`` (include/mvbev.h)."""
     _fields_ = [("w", ctypes.c_void_p), ("C", ctypes.c_int64), ("k", ctypes.c_int64),
                 ("slice_mask", ctypes.c_uint64), ("finite", ctypes.c_int32)]
+
+
+class LossPoints(ctypes.Structure):
+    """``mvbev_loss_points`` (include/mvbev.h); all pointers None: a dense item."""
+    _fields_ = [("cells", ctypes.c_void_p), ("values", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("Ht", ctypes.c_int64), ("Wt", ctypes.c_int64)]
 
 
 class ImgHeadItem(ctypes.Structure):
@@ -471,6 +478,9 @@ def _declare(lib):
     lib.mvbev_gaussian_mse_f32.restype = ctypes.c_int
     lib.mvbev_gaussian_mse_f32.argtypes = [items, ctypes.c_int, _i64, ctypes.POINTER(LossKernel), ctypes.c_int,
                                            ctypes.c_float, ctypes.c_int, _p, _i64, _p]
+    lib.mvbev_gaussian_mse_points_f32.restype = ctypes.c_int
+    lib.mvbev_gaussian_mse_points_f32.argtypes = [items, ctypes.POINTER(LossPoints)] + \
+        lib.mvbev_gaussian_mse_f32.argtypes[1:]
     lib.mvbev_loss_finalize_f32.restype = ctypes.c_int
     lib.mvbev_loss_finalize_f32.argtypes = [items, ctypes.c_int, _i64, _p, _i64, ctypes.c_int, _p, _p, _p]
     lib.mvbev_gaussian_mse_backward_f32.restype = ctypes.c_int

@@ -4,6 +4,8 @@
 //   F.mse_loss(x, target)                                               -> its partials + loss_finalize_kernel
 // applied once to the map and once per view (trainer.py:43-47), with the per-batch counts of
 // trainer.py:51-54 from the same pass, and the backward grad_x = g w 2/numel (x - t).
+// An item's target is the dense tensor or the list of its non-zero cells (mvbev_loss_points): the
+// conv kernel then scatters the cells into its tile itself and the item needs no pooling launch.
 //
 // One launch covers every item of a step (the mvbev_warp_view idiom: a by-value argument pack of
 // at most kLossMaxItems items, workgroups numbered through the items).  Nothing here uses float
@@ -115,11 +117,28 @@ struct MseItem {
   uint64_t slices;
   int32_t C, h, w, k, tiles_x, tiles_y, blk0, finite;
 };
+// A point item's target: the non-zero cells of the logical [B][C][Ht][Wt] target (mvbev_loss_points).
+// cells == nullptr: a dense item, staged from MseItem::src.
+struct MsePoints {
+  const int32_t* cells;  // [n][3]: channel, row, column; batch item b owns [offs[b], offs[b + 1])
+  const float* vals;     // [n], >= 0
+  const int32_t* offs;   // [B + 1]
+  int32_t Ht, Wt;
+};
 struct MseArgs {
   MseItem it[kLossMaxItems];
+  MsePoints pt[kLossMaxItems];
   int32_t n, stats_item;
   float thres;
 };
+
+// The pooled positions whose adaptive_max_pool2d window [floor(i in / out), ceil((i + 1) in / out))
+// holds source position p: floor(p out / in) .. ceil((p + 1) out / in) - 1 (one position when in is
+// a multiple of out, up to two for uneven windows, a run of ceil(out / in) + 1 at most when in < out).
+__host__ __device__ inline void pooled_range(int64_t p, int64_t in, int64_t out, int& first, int& last) {
+  first = (int)((p * out) / in);
+  last = (int)(((p + 1) * out + in - 1) / in) - 1;
+}
 
 // The kernel's taps are read through the constant address space: nothing writes them while the
 // kernel runs, and only there can the compiler turn a load at a wave-uniform address into a scalar
@@ -183,18 +202,45 @@ __global__ __launch_bounds__(kLossThreads) void gaussian_mse_kernel(MseArgs a, d
   if (tid == 0) nz_mask = 0;
   __syncthreads();
   unsigned nz = 0;
-  for (int ci = 0; ci < C; ++ci) {
-    const float* sp = it.src + b * it.ss[0] + ci * it.ss[1];
-    float* tp = tile + ci * plane;
-    for (int ry = tid >> 6; ry < rows; ry += kLossThreads / 64) {
-      const int gy = y0 - r + ry;
-      const bool iny = gy >= 0 && gy < h;
-      for (int rx = tid & 63; rx < cols; rx += 64) {
-        const int gx = x0 - r + rx;
-        float v = 0.f;
-        if (iny && gx >= 0 && gx < w) v = sp[gy * it.ss[2] + gx * it.ss[3]];
-        tp[ry * pitch + rx] = v;
-        if (v != 0.f) nz |= 1u << ci;  // NaN counts as non-zero
+  const MsePoints& pt = a.pt[ii];
+  if (pt.cells) {
+    // a point item: zero the tile, then raise every pooled cell whose window holds a point to the
+    // point's value.  Values are >= 0, where the integer order of the bits is the float order, and a
+    // maximum does not depend on the order of arrival: the tile is what the dense path stages from
+    // the pooled dense target, word for word.
+    for (int i = tid; i < C * plane; i += kLossThreads) tile[i] = 0.f;
+    __syncthreads();
+    const int p1 = pt.offs[b + 1];
+    for (int p = pt.offs[b] + tid; p < p1; p += kLossThreads) {
+      const int ci = pt.cells[3 * (int64_t)p];
+      const float v = pt.vals[p];
+      if ((unsigned)ci >= (unsigned)C || !(v > 0.f)) continue;
+      int i0, i1, j0, j1;
+      pooled_range(pt.cells[3 * (int64_t)p + 1], pt.Ht, h, i0, i1);
+      pooled_range(pt.cells[3 * (int64_t)p + 2], pt.Wt, w, j0, j1);
+      // clip to the image, then to the tile plus its halo
+      const int ry0 = max(max(i0, 0) - (y0 - r), 0), ry1 = min(min(i1, h - 1) - (y0 - r), rows - 1);
+      const int rx0 = max(max(j0, 0) - (x0 - r), 0), rx1 = min(min(j1, w - 1) - (x0 - r), cols - 1);
+      if (ry0 > ry1 || rx0 > rx1) continue;
+      nz |= 1u << ci;
+      int* tp = reinterpret_cast<int*>(tile + ci * plane);
+      for (int ry = ry0; ry <= ry1; ++ry)
+        for (int rx = rx0; rx <= rx1; ++rx) atomicMax(tp + ry * pitch + rx, __float_as_int(v));
+    }
+  } else {
+    for (int ci = 0; ci < C; ++ci) {
+      const float* sp = it.src + b * it.ss[0] + ci * it.ss[1];
+      float* tp = tile + ci * plane;
+      for (int ry = tid >> 6; ry < rows; ry += kLossThreads / 64) {
+        const int gy = y0 - r + ry;
+        const bool iny = gy >= 0 && gy < h;
+        for (int rx = tid & 63; rx < cols; rx += 64) {
+          const int gx = x0 - r + rx;
+          float v = 0.f;
+          if (iny && gx >= 0 && gx < w) v = sp[gy * it.ss[2] + gx * it.ss[3]];
+          tp[ry * pitch + rx] = v;
+          if (v != 0.f) nz |= 1u << ci;  // NaN counts as non-zero
+        }
       }
     }
   }
@@ -388,6 +434,70 @@ static int64_t loss_item_blocks(const mvbev_loss_item& it, int64_t B) {
   return B * ceil_div(it.h, (int64_t)kLossTH) * ceil_div(it.w, (int64_t)kLossTW);
 }
 
+// mvbev_gaussian_mse_f32 (points == nullptr) and mvbev_gaussian_mse_points_f32
+static int launch_gaussian_mse(const mvbev_loss_item* items, const mvbev_loss_points* points, int n, int64_t B,
+                               const mvbev_loss_kernel* kernels, int nkernels, float cls_thres, int stats_item,
+                               double* partials, int64_t npartials, void* stream) {
+  const int st = loss_check_items(items, n, B);
+  if (st != MVBEV_OK) return st;
+  if (!kernels || !partials) return MVBEV_ERR_NULL;
+  if (nkernels <= 0) return MVBEV_ERR_RANK;
+  if (stats_item < -1 || stats_item >= n) return MVBEV_ERR_SHAPE;
+  MseArgs a = {};
+  a.n = n, a.stats_item = stats_item, a.thres = cls_thres;
+  int64_t blocks = 0, lds = 0;
+  for (int i = 0; i < n; ++i) {
+    const mvbev_loss_item& it = items[i];
+    if (it.kernel_id < 0 || it.kernel_id >= nkernels) return MVBEV_ERR_SHAPE;
+    const mvbev_loss_kernel& kn = kernels[it.kernel_id];
+    if (kn.k <= 0) return MVBEV_ERR_RANK;
+    if (kn.k % 2 == 0 || kn.C != it.C || kn.k > 1023) return MVBEV_ERR_SHAPE;
+    const int k = (int)kn.k;
+    const int64_t bytes = it.C * (kLossTH + k - 1) * (int64_t)loss_pitch(k) * (int64_t)sizeof(float);
+    if (bytes > kLossLdsBytes - 256) return MVBEV_ERR_SHAPE;  // 256 B: the kernel's static LDS
+    const bool same = it.Ht == it.h && it.Wt == it.w;
+    if (i == stats_item && (!same || !it.x)) return MVBEV_ERR_SHAPE;
+    // a point record: all three pointers or none (none: a dense item), the item's own Ht x Wt
+    const mvbev_loss_points* rec = points ? points + i : nullptr;
+    const bool pts = rec && (rec->cells || rec->values || rec->offsets);
+    if (pts) {
+      if (!rec->cells || !rec->values || !rec->offsets) return MVBEV_ERR_NULL;
+      if (rec->Ht != it.Ht || rec->Wt != it.Wt || it.Ht > INT32_MAX || it.Wt > INT32_MAX) return MVBEV_ERR_SHAPE;
+      if (!kn.w || (!it.x && !it.t_out)) return MVBEV_ERR_NULL;
+    } else if (!kn.w || !it.target || (!same && !it.pooled) || (!it.x && !it.t_out)) {
+      return MVBEV_ERR_NULL;
+    }
+    if (!it.x && it.diff) return MVBEV_ERR_NULL;
+    lds = std::max(lds, bytes);
+    MseItem& m = a.it[i];
+    m.x = it.x;
+    m.src = same ? it.target : it.pooled;
+    const int64_t contiguous[4] = {it.C * it.h * it.w, it.h * it.w, it.w, 1};
+    for (int d = 0; d < 4; ++d) {
+      m.xs[d] = it.x_strides[d];
+      m.ss[d] = same ? it.t_strides[d] : contiguous[d];
+    }
+    m.wk = kn.w, m.t_out = it.t_out, m.diff = it.diff, m.slices = kn.slice_mask;
+    m.C = (int32_t)it.C, m.h = (int32_t)it.h, m.w = (int32_t)it.w, m.k = k, m.finite = kn.finite;
+    m.tiles_x = (int32_t)ceil_div(it.w, (int64_t)kLossTW);
+    m.tiles_y = (int32_t)ceil_div(it.h, (int64_t)kLossTH);
+    if (pts) {
+      MsePoints& q = a.pt[i];
+      q.cells = rec->cells, q.vals = rec->values, q.offs = rec->offsets;
+      q.Ht = (int32_t)it.Ht, q.Wt = (int32_t)it.Wt;
+      m.src = nullptr;
+    }
+    m.blk0 = (int32_t)blocks;
+    blocks += loss_item_blocks(it, B);
+    if (blocks > INT32_MAX) return MVBEV_ERR_SHAPE;
+  }
+  if (npartials < 4 * blocks) return MVBEV_ERR_SHAPE;
+  hipLaunchKernelGGL(gaussian_mse_kernel, dim3((unsigned)blocks), dim3(kLossThreads), (size_t)lds, as_stream(stream),
+                     a, partials);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
 }  // namespace mvbev
 
 extern "C" {
@@ -429,50 +539,16 @@ int64_t mvbev_gaussian_mse_blocks(const mvbev_loss_item* items, int n, int64_t B
 int mvbev_gaussian_mse_f32(const mvbev_loss_item* items, int n, int64_t B, const mvbev_loss_kernel* kernels,
                            int nkernels, float cls_thres, int stats_item, double* partials, int64_t npartials,
                            void* stream) {
-  using namespace mvbev;
-  const int st = loss_check_items(items, n, B);
-  if (st != MVBEV_OK) return st;
-  if (!kernels || !partials) return MVBEV_ERR_NULL;
-  if (nkernels <= 0) return MVBEV_ERR_RANK;
-  if (stats_item < -1 || stats_item >= n) return MVBEV_ERR_SHAPE;
-  MseArgs a = {};
-  a.n = n, a.stats_item = stats_item, a.thres = cls_thres;
-  int64_t blocks = 0, lds = 0;
-  for (int i = 0; i < n; ++i) {
-    const mvbev_loss_item& it = items[i];
-    if (it.kernel_id < 0 || it.kernel_id >= nkernels) return MVBEV_ERR_SHAPE;
-    const mvbev_loss_kernel& kn = kernels[it.kernel_id];
-    if (kn.k <= 0) return MVBEV_ERR_RANK;
-    if (kn.k % 2 == 0 || kn.C != it.C || kn.k > 1023) return MVBEV_ERR_SHAPE;
-    const int k = (int)kn.k;
-    const int64_t bytes = it.C * (kLossTH + k - 1) * (int64_t)loss_pitch(k) * (int64_t)sizeof(float);
-    if (bytes > kLossLdsBytes - 256) return MVBEV_ERR_SHAPE;  // 256 B: the kernel's static LDS
-    const bool same = it.Ht == it.h && it.Wt == it.w;
-    if (i == stats_item && (!same || !it.x)) return MVBEV_ERR_SHAPE;
-    if (!kn.w || !it.target || (!same && !it.pooled) || (!it.x && !it.t_out)) return MVBEV_ERR_NULL;
-    if (!it.x && it.diff) return MVBEV_ERR_NULL;
-    lds = std::max(lds, bytes);
-    MseItem& m = a.it[i];
-    m.x = it.x;
-    m.src = same ? it.target : it.pooled;
-    const int64_t contiguous[4] = {it.C * it.h * it.w, it.h * it.w, it.w, 1};
-    for (int d = 0; d < 4; ++d) {
-      m.xs[d] = it.x_strides[d];
-      m.ss[d] = same ? it.t_strides[d] : contiguous[d];
-    }
-    m.wk = kn.w, m.t_out = it.t_out, m.diff = it.diff, m.slices = kn.slice_mask;
-    m.C = (int32_t)it.C, m.h = (int32_t)it.h, m.w = (int32_t)it.w, m.k = k, m.finite = kn.finite;
-    m.tiles_x = (int32_t)ceil_div(it.w, (int64_t)kLossTW);
-    m.tiles_y = (int32_t)ceil_div(it.h, (int64_t)kLossTH);
-    m.blk0 = (int32_t)blocks;
-    blocks += loss_item_blocks(it, B);
-    if (blocks > INT32_MAX) return MVBEV_ERR_SHAPE;
-  }
-  if (npartials < 4 * blocks) return MVBEV_ERR_SHAPE;
-  hipLaunchKernelGGL(gaussian_mse_kernel, dim3((unsigned)blocks), dim3(kLossThreads), (size_t)lds, as_stream(stream),
-                     a, partials);
-  MVBEV_CHECK_LAUNCH();
-  return MVBEV_OK;
+  return mvbev::launch_gaussian_mse(items, nullptr, n, B, kernels, nkernels, cls_thres, stats_item, partials,
+                                    npartials, stream);
+}
+
+int mvbev_gaussian_mse_points_f32(const mvbev_loss_item* items, const mvbev_loss_points* points, int n, int64_t B,
+                                  const mvbev_loss_kernel* kernels, int nkernels, float cls_thres, int stats_item,
+                                  double* partials, int64_t npartials, void* stream) {
+  if (!points) return MVBEV_ERR_NULL;
+  return mvbev::launch_gaussian_mse(items, points, n, B, kernels, nkernels, cls_thres, stats_item, partials,
+                                    npartials, stream);
 }
 
 int mvbev_loss_finalize_f32(const mvbev_loss_item* items, int n, int64_t B, const double* partials,

@@ -2,8 +2,8 @@
 
 Drop-ins for ``multiview_detector/loss/gaussian_mse.py:7-20`` and for the loss / precision-recall
 lines of ``multiview_detector/trainer.py:43-56``, on the HIP kernels of ``libmvbev.so``
-(``mvbev_adaptive_max_pool_f32``, ``mvbev_gaussian_mse_f32``, ``mvbev_loss_finalize_f32``,
-``mvbev_gaussian_mse_backward_f32``; ``mvdet_amd/csrc/loss.hip``):
+(``mvbev_adaptive_max_pool_f32``, ``mvbev_gaussian_mse_f32`` / ``mvbev_gaussian_mse_points_f32``,
+``mvbev_loss_finalize_f32``, ``mvbev_gaussian_mse_backward_f32``; ``mvdet_amd/csrc/loss.hip``):
 
 * ``GaussianMSE`` — the reference's ``nn.Module``: ``forward(x, target, kernel)`` and
   ``_traget_transform(x, target, kernel)`` (the reference's spelling; ``trainer.py:131`` calls it).
@@ -12,6 +12,10 @@ lines of ``multiview_detector/trainer.py:43-56``, on the HIP kernels of ``libmvb
   map and every view and one finalize launch; the backward is one launch.
 * ``gaussian_kernels(grid_reduce, img_reduce) -> (map_kernel, img_kernel)`` — the closed form of
   ``frameDataset.py:17-18,40-57`` for datasets that carry no kernels (``mvdet_amd.synthetic``).
+
+A target is a dense fp32 tensor or a ``mvdet_amd.targets.PointTargets`` (its non-zero cells), item
+by item: a point item is pooled by the conv kernel's own staging (no dense tensor, no pooled scratch,
+no pooling launch) and gives bitwise the result of its ``dense()``.
 
 Everything is fp32.  The gradient goes to ``x`` only, as in the reference (its conv runs under
 ``no_grad`` and the targets / kernels require none).  Non-finite values in ``target`` are not
@@ -28,6 +32,7 @@ from torch import nn
 
 from . import _native
 from .ops import _require_cuda, _stream
+from .targets import PointTargets
 
 MAX_ITEMS = 16  # kLossMaxItems (csrc/loss.hip)
 MAX_C = 8       # kLossMaxC: the slice mask is 64 bits
@@ -128,9 +133,14 @@ kernel_cache = _PlanCache()
 
 
 def _check_pair(x, target, kernel):
+    """``target``: a dense tensor or a ``PointTargets``, whose logical shape and device follow the
+    dense target's rules."""
     for name, t in (("x", x), ("target", target)):
+        if name == "target" and isinstance(t, PointTargets):
+            continue  # 4-D and fp32 by construction
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+            raise TypeError(f"{name} must be a tensor{' or a PointTargets' if name == 'target' else ''}, "
+                            f"got {type(t).__name__}")
         if t.dim() != 4:
             raise ValueError(f"{name} must be 4-D [B,C,H,W], got {t.dim()}-D")
         if t.dtype != torch.float32:
@@ -180,6 +190,9 @@ class _Launch:
         shapes = [tuple(x.shape) for x in xs]
         sizes = [int(np.prod(s)) for s in shapes]
         same = [tuple(t.shape[2:]) == s[2:] for t, s in zip(targets, shapes)]
+        # a point item is pooled by the conv kernel's own staging: no scratch, no pooling launch
+        point = [isinstance(t, PointTargets) for t in targets]
+        self.points = (_native.LossPoints * self.n)() if any(point) else None
 
         def slices(want):
             flat = torch.empty(sum(n for n, w in zip(sizes, want) if w), dtype=torch.float32, device=dev)
@@ -188,28 +201,44 @@ class _Launch:
                 out.append(flat[off:off + n].view(s) if w else None)
                 off += n if w else 0
             return out
-        pooled = slices([not s for s in same])
+        pooled = slices([not s and not p for s, p in zip(same, point)])
         self.t_out = slices([want_t] * self.n)
         self.diff = slices([want_diff and with_x] * self.n)
         self.keep.append(pooled)
         for i, (x, t, w) in enumerate(zip(xs, targets, weights)):
             _, C, h, wd = shapes[i]
             ptr = [b[i].data_ptr() if b[i] is not None else None for b in (pooled, self.t_out, self.diff)]
+            if point[i]:
+                self.points[i] = _native.LossPoints(*t.pointers(), t.shape[2], t.shape[3])
             self.items[i] = _native.LossItem(
-                x.data_ptr() if with_x else None, _native.strides4(x), t.data_ptr(), _native.strides4(t), C, h, wd,
+                x.data_ptr() if with_x else None, _native.strides4(x), None if point[i] else t.data_ptr(),
+                _native._i64x4() if point[i] else _native.strides4(t), C, h, wd,
                 t.shape[2], t.shape[3], ptr[0], ptr[1], ptr[2], ids[i], float(w))
+        # the dense items that need pooling, for the pooling launch (none: no launch)
+        to_pool = [i for i in range(self.n) if pooled[i] is not None]
+        self.pool_items = (_native.LossItem * len(to_pool))(*[self.items[i] for i in to_pool]) if to_pool else None
+        self.n_pooled = len(to_pool)  # pooled scratch buffers allocated
+        self.launches = []            # what forward() enqueued, in order: "pool", "mse", "finalize"
         self.stream = _stream(xs[0])
 
     def forward(self, finalize=True):
         lib, n, B = self.lib, self.n, self.B
-        _native.check(lib.mvbev_adaptive_max_pool_f32(self.items, n, B, self.stream), "mvbev_adaptive_max_pool_f32")
+        if self.pool_items is not None:
+            _native.check(lib.mvbev_adaptive_max_pool_f32(self.pool_items, len(self.pool_items), B, self.stream),
+                          "mvbev_adaptive_max_pool_f32")
+            self.launches.append("pool")
         blocks = int(lib.mvbev_gaussian_mse_blocks(self.items, n, B))
         if blocks <= 0:
             raise _native.NativeError("mvbev_gaussian_mse_blocks: the items do not fit one launch")
         partials = torch.empty(4 * blocks, dtype=torch.float64, device=self.dev)
-        _native.check(lib.mvbev_gaussian_mse_f32(self.items, n, B, self.kernels, len(self.plans), self.cls_thres,
-                                                 self.stats_item, partials.data_ptr(), partials.numel(), self.stream),
-                      "mvbev_gaussian_mse_f32")
+        tail = (n, B, self.kernels, len(self.plans), self.cls_thres, self.stats_item, partials.data_ptr(),
+                partials.numel(), self.stream)
+        if self.points is None:
+            _native.check(lib.mvbev_gaussian_mse_f32(self.items, *tail), "mvbev_gaussian_mse_f32")
+        else:
+            _native.check(lib.mvbev_gaussian_mse_points_f32(self.items, self.points, *tail),
+                          "mvbev_gaussian_mse_points_f32")
+        self.launches.append("mse")
         # everything that reads the predictions, the targets and the pooled scratch is enqueued (the
         # allocator keeps their memory until this stream is past it): the backward needs only diff
         self.keep = None
@@ -221,6 +250,7 @@ class _Launch:
                                                   self.stats_item, loss.data_ptr(),
                                                   stats.data_ptr() if stats is not None else None, self.stream),
                       "mvbev_loss_finalize_f32")
+        self.launches.append("finalize")
         return loss, stats
 
     def backward(self, grad_out: torch.Tensor, wanted):
@@ -261,7 +291,8 @@ class GaussianMSE(nn.Module):
     """Drop-in for ``multiview_detector.loss.gaussian_mse.GaussianMSE``:
     ``mse_loss(x, conv2d(adaptive_max_pool2d(target, x.shape[2:]), kernel, padding=(k - 1) / 2))``.
 
-    ``x`` [B,C,h,w] and ``target`` [B,C,Ht,Wt] are fp32 tensors on one GPU; ``kernel`` [C,C,k,k]
+    ``x`` [B,C,h,w] and ``target`` [B,C,Ht,Wt] are fp32 tensors on one GPU (``target`` may be a
+    ``PointTargets`` of that logical shape instead); ``kernel`` [C,C,k,k]
     (odd k) may live on the host, as ``dataset.map_kernel`` does: it is uploaded once and its plan
     cached until it changes in place.  The gradient goes to ``x`` only.  Non-finite values in
     ``target`` are not defined behaviour (ground-truth maps are counts)."""
@@ -294,7 +325,8 @@ def detection_loss(map_res, imgs_res, map_gt, imgs_gt, map_kernel, img_kernel, a
         recall = tp / (tp + fn + 1e-4)
 
     Targets must be on the predictions' device (move them with ``.to(device, non_blocking=True)``);
-    the kernels may stay on the host."""
+    the kernels may stay on the host.  ``map_gt`` and every ``imgs_gt[v]`` may each be a dense tensor or
+    a ``PointTargets`` (``mvdet_amd.targets.pack_step`` uploads a whole step's in one copy)."""
     imgs_res, imgs_gt = list(imgs_res), list(imgs_gt)
     if len(imgs_res) != len(imgs_gt):
         raise ValueError(f"{len(imgs_res)} view predictions but {len(imgs_gt)} view targets")

@@ -1131,6 +1131,37 @@ int mvbev_upsample_map_f32(const float* x, int64_t B, int64_t h, int64_t w, int6
 int mvbev_upsample_map_backward_f32(const float* dy, int64_t B, int64_t h, int64_t w, int64_t Ho, int64_t Wo,
                                     float* dx, void* stream);
 
+/* ---- the camera-frame front (added after 12500; mvbev_version() stays 12500) ----
+ *
+ * main.py:38-40's T.Compose([T.Resize([h, w]), T.ToTensor(), normalize]) of frameDataset.py:127-133 for every view
+ * and batch item in one launch, bit for bit: Pillow's 8-bit bilinear resize (two separable passes with 22-bit
+ * fixed-point coefficients, horizontal first, acc = 1 << 21; acc += px * coef; clamp(acc >> 22, 0, 255) in int32
+ * after each pass), then one table look-up per channel byte for ToTensor + Normalize.
+ *   views[i]   view i's decoded frames [B][H][W][3] uint8 ("RGB": pixel stride 3, channel stride 1) with batch
+ *              and row strides in bytes (>= 0, any alignment: a slice of a wider buffer is read in place)
+ *   bounds_x   [w][2] int32 (first input column, tap count) and coef_x [w][ksx] int32, the horizontal table;
+ *   bounds_y   [h][2] and coef_y [h][ksy], the vertical table (device memory; mvdet_amd.frames.resample_table
+ *              restates Pillow's precompute_coeffs / normalize_coeffs_8bpc).  Bounds are clamped to the image on
+ *              the device.  An axis of equal sizes has the table of one tap of weight 1 << 22: a copy.
+ *   lut        [3][256] fp32 (device): the value of byte v in channel c
+ *   out        [B][nviews][3][h][w] fp32 at element strides out_strides (>= 0); a wave stores contiguous runs when
+ *              the channel stride is 1 (each view in torch's channels_last format) and when the column stride is 1
+ *              (NCHW); both hold bitwise-equal values
+ * No allocation, no synchronisation.  Range: 1 <= nviews <= 16, 1 <= ksx, ksy <= 64, the output below 2^31
+ * elements, and a staged input box that fits 64 KB of LDS at the smallest tile (8 x 32 outputs: downscales up to
+ * 7x on both axes, any upscale), else MVBEV_ERR_SHAPE; a size <= 0 is MVBEV_ERR_RANK, a negative stride
+ * MVBEV_ERR_STRIDE, a missing pointer MVBEV_ERR_NULL. */
+typedef struct mvbev_frame_view {
+  const void* src;
+  int64_t batch_stride; /* bytes */
+  int64_t row_stride;   /* bytes */
+} mvbev_frame_view;
+
+int mvbev_frames_resize_normalize_u8(const mvbev_frame_view* views, int nviews, int64_t B, int64_t H, int64_t W,
+                                     int64_t h, int64_t w, const int32_t* bounds_x, const int32_t* coef_x, int ksx,
+                                     const int32_t* bounds_y, const int32_t* coef_y, int ksy, const float* lut,
+                                     float* out, const int64_t out_strides[5], void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,9 @@ Public surface (mirrors the reference's):
   (``mvdet_amd.variants``); ``ImageProjection`` — its front: image resize, warp, concat and coord channels as one
   launch (``mvdet_amd.img_proj``); ``DenseFuseHead`` — its ground-plane head on the dense world feature: the three
   convs and the closing bilinear upsample, with a native backward (``mvdet_amd.dense_head``).
+* ``FrameTransform`` / ``resize_normalize`` — the reference's ``train_trans`` (``main.py:38-40``: Pillow's bilinear
+  ``T.Resize``, ``T.ToTensor``, ``T.Normalize``) on the decoded uint8 frames of every view in one launch, bit for bit
+  (``mvdet_amd.frames``); every detector takes one as ``frame_transform=`` and then accepts the uint8 frames.
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -49,9 +52,12 @@ from . import img_proj  # noqa: F401
 from .img_proj import ImageProjection  # noqa: F401
 from . import dense_head  # noqa: F401
 from .dense_head import DenseFuseHead  # noqa: F401
+from . import frames  # noqa: F401
+from .frames import FrameTransform, resize_normalize  # noqa: F401
 from .variants import ImageProjVariant, NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
            "detection_loss", "gaussian_kernels", "targets", "PointTargets", "pack_step", "img_head", "upsample_relu_conv1x1",
            "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant",
-           "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant"]
+           "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant", "frames",
+           "FrameTransform", "resize_normalize"]

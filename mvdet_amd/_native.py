@@ -137,6 +137,8 @@ EXPORTS = (
     "mvbev_img_proj_forward_f32",
     "mvbev_upsample_map_f32",
     "mvbev_upsample_map_backward_f32",
+    # the camera-frame front (added after 12500; the version stays 12500)
+    "mvbev_frames_resize_normalize_u8",
 )
 IMG_PROJ_PER_PIXEL = 1  # MVBEV_IMG_PROJ_PER_PIXEL
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
@@ -231,6 +233,11 @@ class ImgHeadItem(ctypes.Structure):
                 ("out_strides", ctypes.c_int64 * 4), ("grad_out", ctypes.c_void_p),
                 ("grad_out_strides", ctypes.c_int64 * 4), ("grad_g", ctypes.c_void_p),
                 ("grad_g_strides", ctypes.c_int64 * 4)]
+
+
+class FrameView(ctypes.Structure):
+    """``mvbev_frame_view`` (include/mvbev.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("batch_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64)]
 
 
 class NativeError(RuntimeError):
@@ -529,6 +536,10 @@ def _declare(lib):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
         fn.argtypes = [_p] + [_i64] * 5 + [_p, _p]
+    lib.mvbev_frames_resize_normalize_u8.restype = ctypes.c_int
+    lib.mvbev_frames_resize_normalize_u8.argtypes = ([ctypes.POINTER(FrameView), ctypes.c_int] + [_i64] * 5 +
+                                                     [_p, _p, ctypes.c_int] * 2 +  # bounds, coef, ksize per axis
+                                                     [_p, _p, _i64 * 5, _p])  # lut, out, out_strides, stream
 
 
 def load(path: os.PathLike | str | None = None):

@@ -27,6 +27,11 @@ when grad is required upsample + warp + concat + fusion run as
 upsample + warp), HIP backward (the fused upsample + warp adjoint, conv data/weight/bias
 gradients).  There is no stock-torch fallback for the hot path.
 The library is loaded at construction on a GPU, so a missing build fails there.
+
+``frame_transform=`` (a ``mvdet_amd.frames.FrameTransform``, default None) lets ``forward`` take the decoded frames, a
+uint8 ``[B,N,H,W,3]`` tensor: the reference's ``train_trans`` (``main.py:38-40``) then runs first as one HIP launch and
+its result is what ``forward`` would have been given.  Any other input takes the path above unchanged; the
+``state_dict`` does not hold the transform.
 """
 from __future__ import annotations
 
@@ -48,6 +53,18 @@ class _ViewsDetector(nn.Module):
     ``no_joint_conv_variant.py`` repeat it verbatim): the dataset attributes, the backbone halves, the image
     head, the per-view part of ``forward`` and the reference's helper methods.  A subclass adds its
     ``map_classifier`` between ``_init_views`` and ``_place``, which keeps the reference's ``state_dict`` order."""
+
+    # a ``mvdet_amd.frames.FrameTransform`` (or None): when set, ``forward`` also takes the decoded frames, a uint8
+    # ``[B,N,H,W,3]`` tensor, and runs the transform first.  A plain attribute: the ``state_dict`` does not hold it.
+    frame_transform = None
+
+    def _frames(self, imgs):
+        """``imgs`` as ``forward`` takes them: decoded uint8 frames go through ``frame_transform`` (on the module's
+        device), anything else (the reference's fp32 ``[B,N,3,H,W]``) is returned as it is."""
+        ft = self.frame_transform
+        if ft is not None and ft.takes(imgs):
+            return ft(imgs.to(self._device))
+        return imgs
 
     def _init_views(self, dataset, arch: str, device, channels_last: bool, native_img_head: bool) -> int:
         self.num_cam = dataset.num_cam
@@ -161,8 +178,9 @@ class _ViewsDetector(nn.Module):
 class PerspTransDetector(_ViewsDetector):
     def __init__(self, dataset, arch: str = "resnet18", device=None, precision: str = "bf16x3",
                  wino_conv1: bool = True, wino_conv2: bool = True, channels_last: bool = True,
-                 native_img_head: bool = True):
+                 native_img_head: bool = True, frame_transform=None):
         super().__init__()
+        self.frame_transform = frame_transform
         out_channel = self._init_views(dataset, arch, device, channels_last, native_img_head)
         self.map_classifier = nn.Sequential(nn.Conv2d(out_channel * self.num_cam + 2, 512, 3, padding=1), nn.ReLU(),
                                             nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),
@@ -175,6 +193,7 @@ class PerspTransDetector(_ViewsDetector):
 
     # -- hot path --------------------------------------------------------------------------
     def forward(self, imgs: torch.Tensor, visualize: bool = False):
+        imgs = self._frames(imgs)
         B, N, C, H, W = imgs.shape
         assert N == self.num_cam
         dev = self._device

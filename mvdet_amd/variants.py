@@ -33,6 +33,9 @@ HIP launch (``mvdet_amd.img_proj``: resize + warp + concat + coord channels, bor
 and everything behind it the native dense head (``mvdet_amd.dense_head``: the MFMA convs and the closing upsample,
 in inference and under autograd); ``native_map_head=False`` keeps ``map_classifier`` + ``F.interpolate`` as torch
 ops, the front stays native.  Nothing in front of the backbone has parameters, so the front has no backward.
+
+Every variant takes ``frame_transform=`` as ``PerspTransDetector`` does (``detector._ViewsDetector._frames``): with it,
+``forward`` also accepts the decoded uint8 ``[B,N,H,W,3]`` frames and runs ``mvdet_amd.frames`` on them first.
 """
 from __future__ import annotations
 
@@ -66,8 +69,9 @@ def view_gemm(feats, weight: torch.Tensor, n_views: int):
 
 class NoJointConvVariant(_ViewsDetector):
     def __init__(self, dataset, arch: str = "resnet18", device=None, channels_last: bool = True,
-                 native_img_head: bool = True):
+                 native_img_head: bool = True, frame_transform=None):
         super().__init__()
+        self.frame_transform = frame_transform
         out_channel = self._init_views(dataset, arch, device, channels_last, native_img_head)
         self.map_classifier = nn.Sequential(nn.Conv2d(out_channel * self.num_cam + 2, 512, 1), nn.ReLU(),
                                             nn.Conv2d(512, 1, 1, bias=False))          # :51-53
@@ -76,6 +80,7 @@ class NoJointConvVariant(_ViewsDetector):
         self.head = ProjectSumHead(self.proj_mats, tuple(self.upsample_shape), tuple(self.reducedgrid_shape))
 
     def forward(self, imgs: torch.Tensor, visualize: bool = False):
+        imgs = self._frames(imgs)
         B, N, C, H, W = imgs.shape
         assert N == self.num_cam
         if self._device.type != "cuda":
@@ -92,8 +97,9 @@ class NoJointConvVariant(_ViewsDetector):
 
 class ResProjVariant(_ViewsDetector):
     def __init__(self, dataset, arch: str = "resnet18", device=None, channels_last: bool = True,
-                 native_img_head: bool = True):
+                 native_img_head: bool = True, frame_transform=None):
         super().__init__()
+        self.frame_transform = frame_transform
         self._init_views(dataset, arch, device, channels_last, native_img_head)
         self.map_classifier = nn.Sequential(nn.Conv2d(self.num_cam + 2, 512, 3, padding=1), nn.ReLU(),
                                             nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),
@@ -102,6 +108,7 @@ class ResProjVariant(_ViewsDetector):
         self.head = ProjectThinFuse(self.proj_mats, tuple(self.upsample_shape), tuple(self.reducedgrid_shape))
 
     def forward(self, imgs: torch.Tensor, visualize: bool = False):
+        imgs = self._frames(imgs)
         B, N, C, H, W = imgs.shape
         assert N == self.num_cam
         if self._device.type != "cuda":
@@ -119,8 +126,9 @@ class ResProjVariant(_ViewsDetector):
 
 class ImageProjVariant(_ViewsDetector):
     def __init__(self, dataset, arch: str = "resnet18", device=None, channels_last: bool = True,
-                 native_map_head: bool = True):
+                 native_map_head: bool = True, frame_transform=None):
         super().__init__()
+        self.frame_transform = frame_transform
         self.num_cam = dataset.num_cam
         self.img_shape, self.reducedgrid_shape = list(dataset.img_shape), list(dataset.reducedgrid_shape)
         self.coord_map = make_coord_map(*self.reducedgrid_shape)                    # :24 (not a buffer)
@@ -144,6 +152,7 @@ class ImageProjVariant(_ViewsDetector):
         self.head = DenseFuseHead(tuple(self.reducedgrid_shape))
 
     def forward(self, imgs: torch.Tensor, visualize: bool = False):
+        imgs = self._frames(imgs)
         B, N, C, H, W = imgs.shape
         assert N == self.num_cam
         dev = self._device

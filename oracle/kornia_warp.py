@@ -126,6 +126,32 @@ def warp_perspective(src: torch.Tensor, M: torch.Tensor, dsize, mode: str = "bil
     return F.grid_sample(src, grid, align_corners=align_corners, mode=mode, padding_mode=padding_mode)
 
 
+# --- the warp as a matrix (the adjoint's plan, restated) --------------------------
+
+def warp_from_norm(src: torch.Tensor, m_norm: torch.Tensor, dsize) -> torch.Tensor:
+    """``warp_perspective`` from its ``src_norm_trans_dst_norm`` ([3, 3], shared by the batch) on: meshgrid,
+    ``transform_points``, ``grid_sample`` — in ``src``'s dtype throughout (float64: the same steps with no fp32
+    rounding anywhere, the meshgrid included)."""
+    h_out, w_out = dsize
+    grid = create_meshgrid(h_out, w_out, True, dtype=src.dtype).repeat(src.shape[0], 1, 1, 1)
+    grid = transform_points(m_norm.to(src.dtype)[None, None, None], grid)
+    return F.grid_sample(src, grid, align_corners=True, mode="bilinear", padding_mode="zeros")
+
+
+def sampling_matrix(m_norm: torch.Tensor, src_hw, dst_hw, dtype: torch.dtype = torch.float32,
+                    backbone_hw=None) -> torch.Tensor:
+    """S [ho * wo, h * w] with ``warp(x).flatten() == S @ x.flatten()`` per plane: column p is the warp of the
+    unit image e_p.  ``backbone_hw``: of the fused upsample + warp instead (``F.interpolate(bilinear)`` from
+    ``backbone_hw`` to ``src_hw``, then the warp), columns over the backbone pixels.  Its transpose is what a
+    plan of the adjoint holds: the entries of column p are the output samples that touch source pixel p."""
+    h, w = backbone_hw if backbone_hw is not None else src_hw
+    basis = torch.eye(h * w, dtype=dtype).reshape(1, h * w, h, w)
+    if backbone_hw is not None:
+        basis = F.interpolate(basis, tuple(src_hw), mode="bilinear")
+    out = warp_from_norm(basis, m_norm, dst_hw)  # [1, h * w, ho, wo]
+    return out[0].reshape(h * w, -1).t().contiguous()
+
+
 # --- float64 closed form (independent pin) ---------------------------------------
 
 def closed_form_warp_f64(src: np.ndarray, M: np.ndarray, dsize) -> np.ndarray:

@@ -65,6 +65,44 @@ def assert_parity(got, ref, what="", normwise_tol=1e-3):
     return s
 
 
+def parity_stats_sliced(got, ref, dims):
+    """``parity_stats`` with the scale max|ref| taken over ``dims`` only: every index of the other dimensions
+    is a slice judged on its own scale (elementwise bound and normwise error alike).  Returns the worst
+    slice's normwise error, the elementwise count over all slices and the smallest / largest slice scale.  A
+    slice whose reference is identically zero must be exactly zero."""
+    got, ref = to_np(got), to_np(ref)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    dims = sorted(d % ref.ndim for d in dims)
+    keep = [d for d in range(ref.ndim) if d not in dims]
+    nsl = int(np.prod([ref.shape[d] for d in keep])) if keep else 1
+    got = np.transpose(got, keep + dims).reshape(nsl, -1)
+    ref = np.transpose(ref, keep + dims).reshape(nsl, -1)
+    nf_g, nf_r = ~np.isfinite(got), ~np.isfinite(ref)
+    assert np.array_equal(nf_g, nf_r), f"non-finite pattern differs ({int(nf_g.sum())} vs {int(nf_r.sum())})"
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), "NaN pattern differs"
+    fin = ~nf_r
+    scale = np.where(fin, np.abs(ref), 0.0).max(axis=1)
+    diff = np.where(fin, np.abs(np.where(fin, got, 0.0) - np.where(fin, ref, 0.0)), 0.0)
+    zero = scale == 0
+    assert not diff[zero].any(), f"{int((diff[zero] != 0).sum())} non-zero entries in slices whose reference is zero"
+    nz = ~zero
+    if not nz.any():
+        return dict(normwise=0.0, n_bad=0, max_abs=0.0, scale_min=0.0, scale_max=0.0, slices=nsl)
+    normwise = float((diff[nz].max(axis=1) / scale[nz]).max())
+    bound = RTOL * np.where(fin, np.abs(ref), 0.0) + ATOL_FRAC * scale[:, None]
+    n_bad = int((diff > bound).sum())
+    return dict(normwise=normwise, n_bad=n_bad, max_abs=float(diff.max()), scale_min=float(scale[nz].min()),
+                scale_max=float(scale.max()), slices=nsl)
+
+
+def assert_parity_sliced(got, ref, dims, what="", normwise_tol=1e-3):
+    """``assert_parity`` per slice: the same gate with max|ref| taken over ``dims`` instead of the whole tensor,
+    so a small-magnitude slice cannot hide behind a large one."""
+    s = parity_stats_sliced(got, ref, dims)
+    assert s["n_bad"] == 0 and s["normwise"] <= normwise_tol, f"{what}: sliced parity failed {s}"
+    return s
+
+
 def masked_relu(pre, m):
     """torch's ReLU with the sign decision of a given 0/1 pattern ``m`` where ``pre`` is not NaN (the GPU's
     activation pattern: a pre-activation within fp32 rounding of 0 may fall either way): value

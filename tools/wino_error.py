@@ -11,47 +11,14 @@ max|y - ref| / max|ref| and the relative Frobenius error.
 """
 import argparse
 import json
+import sys
+from pathlib import Path
 
 import numpy as np
 
-F33 = dict(
-    m=3,
-    BT=np.array([[2, -1, -2, 1, 0], [0, -2, -1, 1, 0], [0, 2, -3, 1, 0], [0, -1, 0, 1, 0], [0, 2, -1, -2, 1]], float),
-    G=np.array([[1 / 2, 0, 0], [-1 / 2, -1 / 2, -1 / 2], [-1 / 6, 1 / 6, -1 / 6], [1 / 6, 1 / 3, 2 / 3], [0, 0, 1]]),
-    AT=np.array([[1, 1, 1, 1, 0], [0, 1, -1, 2, 0], [0, 1, 1, 4, 1]], float),
-)
-F43 = dict(
-    m=4,
-    BT=np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0],
-                 [0, 2, -1, -2, 1, 0], [0, 4, 0, -5, 0, 1]], float),
-    G=np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6],
-                [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]]),
-    AT=np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]], float),
-)
-
-
-def bf16(x):
-    """Round-to-nearest-even fp32 -> bf16 (as float32 values)."""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(np.float32)
-
-
-def split(x):
-    x = np.asarray(x, dtype=np.float32)
-    hi = bf16(x)
-    return hi, bf16(x - hi)
-
-
-def mm3(a_hi, a_lo, b_hi, b_lo):
-    """[M, K] x [K, N] as the 3 bf16 products accumulated in fp32 (16-deep MFMA chunks, in K order)."""
-    K = a_hi.shape[1]
-    acc = np.zeros((a_hi.shape[0], b_hi.shape[1]), np.float32)
-    for k0 in range(0, K, 16):
-        s = slice(k0, k0 + 16)
-        for a, b in ((a_hi, b_lo), (a_lo, b_hi), (a_hi, b_hi)):  # the kernels' pass order
-            acc = (acc + (a[:, s].astype(np.float64) @ b[s].astype(np.float64)).astype(np.float32)).astype(np.float32)
-    return acc
+# the matrices, the bf16 split and the three-pass product live with the backward tests' emulation
+sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "tests"))
+from bf16x3_ref import F33, F43, mm3, split_np as split  # noqa: E402
 
 
 def wino(form, d, w):

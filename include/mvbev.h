@@ -1162,6 +1162,57 @@ int mvbev_frames_resize_normalize_u8(const mvbev_frame_view* views, int nviews, 
                                      const int32_t* bounds_y, const int32_t* coef_y, int ksy, const float* lut,
                                      float* out, const int64_t out_strides[5], void* stream);
 
+/* ---- CLEAR MOD evaluation (added after 12500; mvbev_version() stays 12500) ----
+ *
+ * The test loop's last step (trainer.py:149-160 -> evaluation/pyeval/CLEAR_MOD_HUN.py) without files, scipy or a
+ * host sync per frame.
+ *
+ * Sync-free detections from the map (mvbev_threshold_points / mvbev_point_nms_ws read their counts on the host):
+ *   mvbev_threshold_points_xy   mvbev_threshold_points' ordered compaction, writing the float positions of
+ *       trainer.py:103, xy[k] = (row, column) * scale in fp32 ((column, row) when swap_xy), scores[k] and the device
+ *       *count.  capacity >= H * W (it cannot overflow), else MVBEV_ERR_SHAPE.
+ *   mvbev_point_nms_dev   mvbev_point_nms_ws with K read from the device int32 *K (clamped to [0, capacity]; K = 0:
+ *       *count = 0).  points / scores / keep hold capacity entries; workspace >=
+ *       mvbev_point_nms_workspace_bytes(capacity, capacity), 4-B aligned.
+ *   mvbev_detections_append   copies the *count kept positions points[keep[i]] (i ascending) to buffer[*cursor ...]
+ *       ([max_dets][2] fp32), advances *cursor and stores it to *frame_end.  A frame that does not fit sets
+ *       *overflow = 1, writes nothing to the buffer and leaves the cursor (*frame_end = *cursor).
+ * One workgroup each; enqueued, no allocation, no host sync. */
+int mvbev_threshold_points_xy(const float* map, int64_t H, int64_t W, float thres, float scale, int swap_xy,
+                              int32_t* count, float* xy, float* scores, int64_t capacity, void* stream);
+int mvbev_point_nms_dev(const float* points, const float* scores, const int32_t* K, int64_t capacity,
+                        float dist_thres, int64_t top_k, int64_t* keep, int32_t* count, void* workspace,
+                        size_t ws_bytes, void* stream);
+int mvbev_detections_append(const float* points, const int64_t* keep, const int32_t* count, int64_t capacity,
+                            float* buffer, int64_t max_dets, int32_t* cursor, int32_t* frame_end,
+                            int32_t* overflow, void* stream);
+
+/* CLEAR_MOD_HUN.py:58-91 for F frames in one launch, one workgroup per frame.  gt [Ng][2] and det [Nd][2] hold the
+ * points (device; dtype: both fp32, both fp64, or fp64 GT with fp32 detections), gt_off / det_off [F + 1] int32
+ * (device) their CSR offsets by frame.  Per frame: the cost of (GT o, detection e) is d = sqrt(dx^2 + dy^2) in fp64
+ * (products and sum rounded separately, correctly rounded sqrt) if d <= td, else 1e6 (so is a NaN / inf distance); the
+ * minimum-cost assignment of the smaller side into the larger (scipy's linear_sum_assignment: shortest augmenting
+ * paths, fp64 duals, costs evaluated on the fly; ties in a column scan go to the lowest column, so two runs are
+ * bitwise equal); a pair counts as matched when d < td (a pair at exactly td is assigned at cost td, not counted).
+ *   n_gt, n_det, matched [F] int32; modp_sum [F] fp64 = sum over the frame's matched GT, in GT order, of 1 - d / td;
+ *   cost [F] fp64 = the assignment's total cost; match [Ng] int32 (may be NULL) = each GT's frame-local detection, or -1.
+ * The host cannot see the frame sizes, so the caller states bounds: max_small >= every frame's min(n_gt, n_det)
+ * (<= MVBEV_CLEAR_MOD_MAX_SMALL), max_large >= every frame's max(n_gt, n_det) (<= MVBEV_CLEAR_MOD_MAX_LARGE), else
+ * MVBEV_ERR_SHAPE before any launch.  The column state of a frame with up to 2048 columns lives in LDS, that of a
+ * larger one in the workspace (>= mvbev_clear_mod_workspace_bytes, 8-B aligned; 0 bytes, and workspace may be NULL,
+ * when max_large <= 2048).  A frame that breaks the stated bounds or whose offsets leave [0, Ng] / [0, Nd] is not run:
+ * matched = -1 (n_gt = n_det = -1 for bad offsets).  No allocation, no host sync. */
+#define MVBEV_CLEAR_MOD_MAX_SMALL 1024
+#define MVBEV_CLEAR_MOD_MAX_LARGE (1 << 20)
+#define MVBEV_EVAL_F32 0
+#define MVBEV_EVAL_F64 1
+#define MVBEV_EVAL_GT_F64_DET_F32 2
+size_t mvbev_clear_mod_workspace_bytes(int64_t Ng, int64_t Nd, int64_t max_large);
+int mvbev_clear_mod_frames(const void* gt, const void* det, int dtype, const int32_t* gt_off, const int32_t* det_off,
+                           int64_t F, int64_t Ng, int64_t Nd, int64_t max_small, int64_t max_large, double td,
+                           int32_t* n_gt, int32_t* n_det, int32_t* matched, double* modp_sum, double* cost,
+                           int32_t* match, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,10 @@ Public surface (mirrors the reference's):
 * ``FrameTransform`` / ``resize_normalize`` — the reference's ``train_trans`` (``main.py:38-40``: Pillow's bilinear
   ``T.Resize``, ``T.ToTensor``, ``T.Normalize``) on the decoded uint8 frames of every view in one launch, bit for bit
   (``mvdet_amd.frames``); every detector takes one as ``frame_transform=`` and then accepts the uint8 frames.
+* ``evaluation`` — drop-ins for ``multiview_detector.evaluation.evaluate.evaluate`` and ``evaluation/pyeval``
+  (``CLEAR_MOD_HUN``, ``evaluateDetection_py``): MODA, MODP, precision and recall with the Hungarian matching of
+  all frames in one launch; ``DetectionEvaluator`` — a test epoch from output maps to the four numbers with
+  no host sync per frame (``mvdet_amd.evaluation``).
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -54,10 +58,12 @@ from . import dense_head  # noqa: F401
 from .dense_head import DenseFuseHead  # noqa: F401
 from . import frames  # noqa: F401
 from .frames import FrameTransform, resize_normalize  # noqa: F401
+from . import evaluation  # noqa: F401
+from .evaluation import DetectionEvaluator, evaluate  # noqa: F401
 from .variants import ImageProjVariant, NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
            "detection_loss", "gaussian_kernels", "targets", "PointTargets", "pack_step", "img_head", "upsample_relu_conv1x1",
            "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant",
            "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant", "frames",
-           "FrameTransform", "resize_normalize"]
+           "FrameTransform", "resize_normalize", "evaluation", "DetectionEvaluator", "evaluate"]

@@ -139,7 +139,15 @@ EXPORTS = (
     "mvbev_upsample_map_backward_f32",
     # the camera-frame front (added after 12500; the version stays 12500)
     "mvbev_frames_resize_normalize_u8",
+    # CLEAR MOD evaluation (added after 12500; the version stays 12500)
+    "mvbev_threshold_points_xy",
+    "mvbev_point_nms_dev",
+    "mvbev_detections_append",
+    "mvbev_clear_mod_workspace_bytes",
+    "mvbev_clear_mod_frames",
 )
+CLEAR_MOD_MAX_SMALL, CLEAR_MOD_MAX_LARGE = 1024, 1 << 20  # MVBEV_CLEAR_MOD_MAX_*
+EVAL_F32, EVAL_F64, EVAL_GT_F64_DET_F32 = 0, 1, 2  # MVBEV_EVAL_*
 IMG_PROJ_PER_PIXEL = 1  # MVBEV_IMG_PROJ_PER_PIXEL
 BEV_SRC_F32, BEV_SRC_F16, BEV_SRC_BACKBONE_F32 = 0, 1, 2  # MVBEV_BEV_SRC_*
 BEV_SRC_CHANNELS_LAST = 16  # MVBEV_BEV_SRC_CHANNELS_LAST (flag)
@@ -540,6 +548,18 @@ def _declare(lib):
     lib.mvbev_frames_resize_normalize_u8.argtypes = ([ctypes.POINTER(FrameView), ctypes.c_int] + [_i64] * 5 +
                                                      [_p, _p, ctypes.c_int] * 2 +  # bounds, coef, ksize per axis
                                                      [_p, _p, _i64 * 5, _p])  # lut, out, out_strides, stream
+    lib.mvbev_threshold_points_xy.restype = ctypes.c_int
+    lib.mvbev_threshold_points_xy.argtypes = [_p, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_int, _p, _p, _p,
+                                              _i64, _p]
+    lib.mvbev_point_nms_dev.restype = ctypes.c_int
+    lib.mvbev_point_nms_dev.argtypes = [_p, _p, _p, _i64, ctypes.c_float, _i64, _p, _p, _p, ctypes.c_size_t, _p]
+    lib.mvbev_detections_append.restype = ctypes.c_int
+    lib.mvbev_detections_append.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]
+    lib.mvbev_clear_mod_workspace_bytes.restype = ctypes.c_size_t
+    lib.mvbev_clear_mod_workspace_bytes.argtypes = [_i64, _i64, _i64]
+    lib.mvbev_clear_mod_frames.restype = ctypes.c_int
+    lib.mvbev_clear_mod_frames.argtypes = ([_p, _p, ctypes.c_int, _p, _p] + [_i64] * 5 + [ctypes.c_double] +
+                                           [_p] * 7 + [ctypes.c_size_t, _p])  # outputs, match, workspace, bytes, stream
 
 
 def load(path: os.PathLike | str | None = None):

@@ -3,7 +3,10 @@
 // Replaces the CPU loop of trainer.py:97-106,148-157:
 //   map_res > cls_thres, nonzero, (frame, x, y, score) rows           -> mvbev_threshold_points
 //   nms(positions, scores, dist_thres, top_k)  (utils/nms.py:7-43)     -> mvbev_point_nms
-// Both are single-workgroup kernels: the data are a few thousand points per frame (an untrained
+// and, for an evaluation epoch that never stops the host (mvdet_amd.evaluation.DetectionEvaluator), the same
+// two with every count left on the device plus the append of a frame's kept positions to an epoch buffer:
+//   mvbev_threshold_points_xy, mvbev_point_nms_dev, mvbev_detections_append
+// All are single-workgroup kernels: the data are a few thousand points per frame (an untrained
 // model can put all 43,200 cells of a cfg2 map over cls_thres, trainer.py:154), so the cost is
 // latency, not bandwidth; what matters is exact agreement with the reference: row-major nonzero
 // order; the NMS candidate order of torch's CPU scores.sort(0) including equal scores
@@ -16,10 +19,13 @@ namespace mvbev {
 
 constexpr int kPPThreads = 1024;
 
-// Ordered stream compaction of map > thres (row-major, torch.nonzero order).
+// Ordered stream compaction of map > thres (row-major, torch.nonzero order).  kXY: the hits as the float
+// positions of trainer.py:103, (row, column) * scale in fp32, swapped to (column, row) when swap.
+template <bool kXY>
 __global__ __launch_bounds__(kPPThreads) void threshold_kernel(const float* __restrict__ map, int n, int W,
                                                                float thres, int* __restrict__ count,
-                                                               int32_t* __restrict__ ij, float* __restrict__ val,
+                                                               int32_t* __restrict__ ij, float* __restrict__ xy,
+                                                               float scale, int swap, float* __restrict__ val,
                                                                int cap) {
   __shared__ int wave_sums[kPPThreads / 64];
   __shared__ int base;
@@ -39,8 +45,14 @@ __global__ __launch_bounds__(kPPThreads) void threshold_kernel(const float* __re
     if (hit) {
       const int o = off + before;
       if (o < cap) {
-        ij[2 * o] = i / W;
-        ij[2 * o + 1] = i - (i / W) * W;
+        const int r = i / W, c = i - r * W;
+        if constexpr (kXY) {
+          xy[2 * o + swap] = (float)r * scale;
+          xy[2 * o + 1 - swap] = (float)c * scale;
+        } else {
+          ij[2 * o] = r;
+          ij[2 * o + 1] = c;
+        }
         val[o] = v;
       }
     }
@@ -386,10 +398,9 @@ __device__ void nms_greedy(const float* __restrict__ pts, int K, int M, float th
 
 // nms.py:7-43 in one workgroup: the candidate order of scores.sort(0) (torch_cpu_sort), its
 // top_k largest from the end, then the greedy loop.
-__global__ __launch_bounds__(kPPThreads) void point_nms_kernel(const float* __restrict__ pts,
-                                                               const float* __restrict__ sc, int K, int M,
-                                                               float thres, SortWs w, int* cand, int* alt,
-                                                               int64_t* __restrict__ keep, int* __restrict__ count) {
+__device__ __forceinline__ void point_nms_body(const float* __restrict__ pts, const float* __restrict__ sc, int K,
+                                               int M, float thres, const SortWs& w, int* cand, int* alt,
+                                               int64_t* __restrict__ keep, int* __restrict__ count) {
   for (int i = threadIdx.x; i < K; i += kPPThreads) {
     w.key[i] = sc[i];
     w.idx[i] = i;
@@ -399,6 +410,52 @@ __global__ __launch_bounds__(kPPThreads) void point_nms_kernel(const float* __re
   for (int j = threadIdx.x; j < M; j += kPPThreads) cand[j] = w.idx[K - 1 - j];  // indices[-top_k:], last first
   __syncthreads();
   nms_greedy(pts, K, M, thres, cand, alt, keep, count);
+}
+
+__global__ __launch_bounds__(kPPThreads) void point_nms_kernel(const float* __restrict__ pts,
+                                                               const float* __restrict__ sc, int K, int M,
+                                                               float thres, SortWs w, int* cand, int* alt,
+                                                               int64_t* __restrict__ keep, int* __restrict__ count) {
+  point_nms_body(pts, sc, K, M, thres, w, cand, alt, keep, count);
+}
+
+// The same with K read from device memory (the count mvbev_threshold_points_xy left), clamped to the
+// capacity the arrays and the workspace were sized for; K = 0 keeps nothing.
+__global__ __launch_bounds__(kPPThreads) void point_nms_dev_kernel(const float* __restrict__ pts,
+                                                                   const float* __restrict__ sc,
+                                                                   const int* __restrict__ Kp, int cap, int64_t top_k,
+                                                                   float thres, SortWs w, int* cand, int* alt,
+                                                                   int64_t* __restrict__ keep, int* __restrict__ count) {
+  const int K = min(max(*Kp, 0), cap);
+  if (K == 0) {
+    if (threadIdx.x == 0) *count = 0;
+    return;
+  }
+  point_nms_body(pts, sc, K, (int)min((int64_t)K, top_k), thres, w, cand, alt, keep, count);
+}
+
+// A frame's kept positions, in keep order, to the epoch buffer at *cursor; *frame_end = the cursor after
+// it.  A frame that does not fit sets *overflow and writes nothing.
+__global__ __launch_bounds__(256) void detections_append_kernel(const float* __restrict__ pts,
+                                                                const int64_t* __restrict__ keep,
+                                                                const int* __restrict__ count, int cap,
+                                                                float* __restrict__ buf, int max_dets, int* cursor,
+                                                                int* frame_end, int* overflow) {
+  const int n = min(max(*count, 0), cap), c = *cursor;
+  const bool fits = c >= 0 && c <= max_dets - n;
+  if (fits) {
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const int64_t k = min<int64_t>(max<int64_t>(keep[i], 0), cap - 1);
+      buf[2 * (int64_t)(c + i)] = pts[2 * k];
+      buf[2 * (int64_t)(c + i) + 1] = pts[2 * k + 1];
+    }
+  }
+  __syncthreads();  // every thread has read *cursor
+  if (threadIdx.x == 0) {
+    if (fits) *cursor = c + n;
+    else *overflow = 1;
+    *frame_end = fits ? c + n : min(max(c, 0), max_dets);
+  }
 }
 
 constexpr int kSortArrays = 14;  // 4-byte arrays of K entries in the workspace: key + SortWs's 13 int arrays
@@ -414,6 +471,18 @@ size_t mvbev_point_nms_workspace_bytes(int64_t K, int64_t top_k) {
   return (size_t)((kSortArrays * K + 2 * M) * (int64_t)sizeof(int));
 }
 
+// the sort's arrays of K entries each at the head of the workspace; returns the first int past them
+static int* sort_ws_layout(mvbev::SortWs& w, void* workspace, int64_t K) {
+  using namespace mvbev;
+  int* p = static_cast<int*>(workspace);
+  w.key = reinterpret_cast<float*>(p);
+  int** arrays[] = {&w.idx, &w.segof, &w.len, &w.depth, &w.act, &w.m, &w.totL, &w.totR, &w.cut, &w.posL, &w.posR,
+                    &w.incL, &w.incR};
+  static_assert(sizeof(arrays) / sizeof(arrays[0]) == kSortArrays - 1, "workspace arrays");
+  for (int a = 0; a < kSortArrays - 1; ++a) *arrays[a] = p + (int64_t)(a + 1) * K;
+  return p + (int64_t)kSortArrays * K;
+}
+
 int mvbev_point_nms_ws(const float* points, const float* scores, int64_t K, float dist_thres, int64_t top_k,
                        int64_t* keep, int32_t* count, void* workspace, size_t ws_bytes, void* stream) {
   using namespace mvbev;
@@ -423,14 +492,8 @@ int mvbev_point_nms_ws(const float* points, const float* scores, int64_t K, floa
   if (ws_bytes < mvbev_point_nms_workspace_bytes(K, top_k)) return MVBEV_ERR_SHAPE;
   if (reinterpret_cast<uintptr_t>(workspace) % 4) return MVBEV_ERR_ALIGN;
   const int M = (int)std::min<int64_t>(K, top_k);
-  int* p = static_cast<int*>(workspace);
   SortWs w;
-  w.key = reinterpret_cast<float*>(p);
-  int** arrays[] = {&w.idx, &w.segof, &w.len, &w.depth, &w.act, &w.m, &w.totL, &w.totR, &w.cut, &w.posL, &w.posR,
-                    &w.incL, &w.incR};
-  static_assert(sizeof(arrays) / sizeof(arrays[0]) == kSortArrays - 1, "workspace arrays");
-  for (int a = 0; a < kSortArrays - 1; ++a) *arrays[a] = p + (int64_t)(a + 1) * K;
-  int* cand = p + (int64_t)kSortArrays * K;
+  int* cand = sort_ws_layout(w, workspace, K);
   int* alt = cand + M;
   hipLaunchKernelGGL(point_nms_kernel, dim3(1), dim3(kPPThreads), 0, as_stream(stream), points, scores, (int)K, M,
                      dist_thres, w, cand, alt, keep, count);
@@ -444,8 +507,52 @@ int mvbev_threshold_points(const float* map, int64_t H, int64_t W, float thres, 
   if (!map || !count || (capacity > 0 && (!ij || !scores))) return MVBEV_ERR_NULL;
   if (H <= 0 || W <= 0 || capacity < 0) return MVBEV_ERR_RANK;
   if (H * W > INT32_MAX || capacity > INT32_MAX) return MVBEV_ERR_SHAPE;
-  hipLaunchKernelGGL(threshold_kernel, dim3(1), dim3(kPPThreads), 0, as_stream(stream), map, (int)(H * W),
-                     (int)W, thres, count, ij, scores, (int)capacity);
+  hipLaunchKernelGGL(threshold_kernel<false>, dim3(1), dim3(kPPThreads), 0, as_stream(stream), map, (int)(H * W),
+                     (int)W, thres, count, ij, static_cast<float*>(nullptr), 0.f, 0, scores, (int)capacity);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
+int mvbev_threshold_points_xy(const float* map, int64_t H, int64_t W, float thres, float scale, int swap_xy,
+                              int32_t* count, float* xy, float* scores, int64_t capacity, void* stream) {
+  using namespace mvbev;
+  if (!map || !count || !xy || !scores) return MVBEV_ERR_NULL;
+  if (H <= 0 || W <= 0) return MVBEV_ERR_RANK;
+  if (H * W > INT32_MAX / 2 || capacity < H * W || capacity > INT32_MAX / 2) return MVBEV_ERR_SHAPE;
+  hipLaunchKernelGGL(threshold_kernel<true>, dim3(1), dim3(kPPThreads), 0, as_stream(stream), map, (int)(H * W),
+                     (int)W, thres, count, static_cast<int32_t*>(nullptr), xy, scale, swap_xy ? 1 : 0, scores,
+                     (int)capacity);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
+int mvbev_point_nms_dev(const float* points, const float* scores, const int32_t* K, int64_t capacity,
+                        float dist_thres, int64_t top_k, int64_t* keep, int32_t* count, void* workspace,
+                        size_t ws_bytes, void* stream) {
+  using namespace mvbev;
+  if (!points || !scores || !K || !keep || !count || !workspace) return MVBEV_ERR_NULL;
+  if (capacity <= 0 || top_k <= 0) return MVBEV_ERR_RANK;
+  if (capacity > ((int64_t)1 << 26)) return MVBEV_ERR_SHAPE;
+  if (ws_bytes < mvbev_point_nms_workspace_bytes(capacity, capacity)) return MVBEV_ERR_SHAPE;
+  if (reinterpret_cast<uintptr_t>(workspace) % 4) return MVBEV_ERR_ALIGN;
+  SortWs w;
+  int* cand = sort_ws_layout(w, workspace, capacity);
+  int* alt = cand + capacity;
+  hipLaunchKernelGGL(point_nms_dev_kernel, dim3(1), dim3(kPPThreads), 0, as_stream(stream), points, scores, K,
+                     (int)capacity, top_k, dist_thres, w, cand, alt, keep, count);
+  MVBEV_CHECK_LAUNCH();
+  return MVBEV_OK;
+}
+
+int mvbev_detections_append(const float* points, const int64_t* keep, const int32_t* count, int64_t capacity,
+                            float* buffer, int64_t max_dets, int32_t* cursor, int32_t* frame_end,
+                            int32_t* overflow, void* stream) {
+  using namespace mvbev;
+  if (!points || !keep || !count || !buffer || !cursor || !frame_end || !overflow) return MVBEV_ERR_NULL;
+  if (capacity <= 0 || max_dets <= 0) return MVBEV_ERR_RANK;
+  if (capacity > ((int64_t)1 << 26) || max_dets > INT32_MAX / 2) return MVBEV_ERR_SHAPE;
+  hipLaunchKernelGGL(detections_append_kernel, dim3(1), dim3(256), 0, as_stream(stream), points, keep, count,
+                     (int)capacity, buffer, (int)max_dets, cursor, frame_end, overflow);
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
 }

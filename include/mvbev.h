@@ -116,6 +116,13 @@ int mvbev_warp_views_f32(const mvbev_warp_view* views, int nviews, int64_t B, in
  * four-row tiles (4 * ceil(out_rows / 16)), 3 per 14 x 16 block; the block's staging-box table is
  * mvbev_warp_wino_boxes' with r3_rows = 4 * ceil(r4_rows / 3) (the same 12-row blocks). */
 #define MVBEV_WARP_WINO43 4
+/* MVBEV_WARP_SRC_BF16 (added after 12500; mvbev_version() stays 12500): the channels-last backbone maps of
+ * mvbev_warp_views_upsampled_wino_rows / _ex are bf16 — with MVBEV_WARP_SRC_F16, which those two entry points now
+ * take too, what a bf16 / fp16 autocast backbone emits.  Only the loads change (a 32-channel group is 64 B): every
+ * value converts to fp32 exactly and all arithmetic is the fp32 form's, so T is bit for bit the T of the same maps
+ * cast to fp32.  Both bits together, or either with maps that are not channels-last sources, return
+ * MVBEV_ERR_SHAPE; mvbev_warp_views_wino_rows / _ex (already-upsampled features) refuse this bit. */
+#define MVBEV_WARP_SRC_BF16 8
 int mvbev_warp_views_split_bf16_ex(const mvbev_warp_view* views, int nviews, int src_is_f16,
                                    int64_t B, int64_t C, int64_t H, int64_t W, int64_t Ho, int64_t Wo,
                                    int flags, void* stream);
@@ -394,7 +401,10 @@ int mvbev_warp_views_wino_rows_ex(const mvbev_warp_view* views, int nviews, int6
  * ABI 11700, both fused warps: channels-last sources (src_strides[1] == 1, [3] >= C, the other strides
  * multiples of 4 floats, 16-B aligned, C % 32 == 0; the same logical [B][C][h][w] tensor in torch's
  * channels_last memory format) run a line-per-pixel form (one 128-B line holds a pixel's 32 channels
- * of a block); same T up to fp32 rounding of the bilinear sums. */
+ * of a block); same T up to fp32 rounding of the bilinear sums.
+ * Added after 12500 (mvbev_version() stays 12500): with MVBEV_WARP_SRC_F16 or MVBEV_WARP_SRC_BF16 in flags the
+ * channels-last maps are fp16 / bf16 (src_strides[1] == 1, [3] >= C, the other strides multiples of 8 elements,
+ * 16-B aligned, C % 32 == 0): the same T, bit for bit, as from those maps cast to fp32. */
 int mvbev_warp_views_upsampled_wino_rows(const mvbev_warp_view* views, int nviews, int64_t B, int64_t C, int64_t h,
                                          int64_t w, int64_t H, int64_t W, int64_t Ho, int64_t Wo, int64_t r3_rows,
                                          int flags, int32_t* nonfinite, int32_t nf_tag, void* stream);
@@ -425,8 +435,9 @@ int mvbev_warp_views_exact_f32(const mvbev_warp_view* views, int nviews, int64_t
                                void* stream);
 /* The same on row windows and fp16 sources (ABI 11900): view i's dst holds out_rows rows of the Ho-row
  * grid starting at grid row row0s[i] (host int32 array) — the exact path in row bands of bounded memory,
- * and the band exchange's windows; src_is_f16: fp16 sources (fp32 math). */
-int mvbev_warp_views_exact_rows(const mvbev_warp_view* views, const int32_t* row0s, int nviews, int src_is_f16,
+ * and the band exchange's windows; src_kind: 0 = fp32 sources, 1 = fp16, 2 = bf16 (added after 12500, the
+ * argument was src_is_f16: 0 and 1 mean what they meant; fp32 math), anything else MVBEV_ERR_SHAPE. */
+int mvbev_warp_views_exact_rows(const mvbev_warp_view* views, const int32_t* row0s, int nviews, int src_kind,
                                 int64_t B, int64_t C, int64_t h, int64_t w, int64_t H, int64_t W, int64_t Ho,
                                 int64_t Wo, int64_t out_rows, const int32_t* gate, int32_t gate_tag, void* stream);
 /* NCHW -> channels-last copy (ABI 11700): view i's fp32 [B][C][H][W] map at views[i].src /
@@ -434,6 +445,10 @@ int mvbev_warp_views_exact_rows(const mvbev_warp_view* views, const int32_t* row
  * view in one launch — the input of the channels-last fused upsample warp for NCHW producers. */
 int mvbev_nchw_to_nhwc_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t C, int64_t H, int64_t W,
                            void* stream);
+/* The same for elements of elem_size bytes (added after 12500; mvbev_version() stays 12500): 4 (as above) or 2 —
+ * fp16 / bf16 maps, a plain transposition of their bits; strides in elements; anything else MVBEV_ERR_SHAPE. */
+int mvbev_nchw_to_nhwc_ex(const mvbev_warp_view* views, int nviews, int elem_size, int64_t B, int64_t C, int64_t H,
+                          int64_t W, void* stream);
 size_t mvbev_conv3x3_packed_bytes_wino(int64_t Cout, int64_t K);
 int mvbev_pack_conv3x3_weight_wino(const float* w, int64_t Cout, int64_t Cin_w, const int32_t* chan_map,
                                    int64_t K, void* w_packed, void* stream);

@@ -145,6 +145,8 @@ EXPORTS = (
     "mvbev_detections_append",
     "mvbev_clear_mod_workspace_bytes",
     "mvbev_clear_mod_frames",
+    # 16-bit backbone maps on the fused upsample warp (added after 12500; the version stays 12500)
+    "mvbev_nchw_to_nhwc_ex",
 )
 CLEAR_MOD_MAX_SMALL, CLEAR_MOD_MAX_LARGE = 1024, 1 << 20  # MVBEV_CLEAR_MOD_MAX_*
 EVAL_F32, EVAL_F64, EVAL_GT_F64_DET_F32 = 0, 1, 2  # MVBEV_EVAL_*
@@ -156,6 +158,8 @@ COUT1_SAME_SIZE_INTERP = 1  # MVBEV_COUT1_SAME_SIZE_INTERP (mvbev_conv3x3_cout1_
 WARP_DST_ZEROED = 1  # MVBEV_WARP_DST_ZEROED
 WARP_SRC_F16 = 2  # MVBEV_WARP_SRC_F16 (mvbev_warp_views_wino_rows, ABI 11900)
 WARP_WINO43 = 4  # MVBEV_WARP_WINO43 (the fused warps write the F(4,3) transform, ABI 12400)
+WARP_SRC_BF16 = 8  # MVBEV_WARP_SRC_BF16 (bf16 channels-last maps of the fused upsample warp, which takes SRC_F16 too)
+EXACT_SRC_F32, EXACT_SRC_F16, EXACT_SRC_BF16 = 0, 1, 2  # mvbev_warp_views_exact_rows' src_kind
 TILES_GRID, TILES_EDGE_STRIP = 0, 1  # MVBEV_TILES_*
 ERR_SHAPE = -2  # MVBEV_ERR_SHAPE
 ERR_DILATION = -6  # MVBEV_ERR_DILATION
@@ -382,6 +386,9 @@ def _declare(lib):
                                                      ctypes.c_size_t, _p, ctypes.c_int32, _p]
     lib.mvbev_nchw_to_nhwc_f32.restype = ctypes.c_int
     lib.mvbev_nchw_to_nhwc_f32.argtypes = [ctypes.POINTER(WarpView), ctypes.c_int, _i64, _i64, _i64, _i64, _p]
+    lib.mvbev_nchw_to_nhwc_ex.restype = ctypes.c_int
+    lib.mvbev_nchw_to_nhwc_ex.argtypes = [ctypes.POINTER(WarpView), ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64,
+                                          _p]
     lib.mvbev_warp_tile_mask.restype = ctypes.c_int
     lib.mvbev_warp_tile_mask.argtypes = [ctypes.POINTER(WarpView), ctypes.c_int, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _i64, _i64, _i64, _p, _p]

@@ -37,6 +37,7 @@ __device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
 template <typename T> __device__ inline float to_f32(T v);
 template <> __device__ inline float to_f32<float>(float v) { return v; }
 template <> __device__ inline float to_f32<__half>(__half v) { return __half2float(v); }
+template <> __device__ inline float to_f32<__bf16>(__bf16 v) { return (float)v; }  // exact: the bits << 16
 template <typename T> __device__ inline T from_f32(float v);
 template <> __device__ inline float from_f32<float>(float v) { return v; }
 template <> __device__ inline __half from_f32<__half>(float v) { return __float2half(v); }

@@ -347,7 +347,25 @@ __global__ __launch_bounds__(kWwThreads) MVBEV_WARP_OCC void warp_up_wino2_kerne
 constexpr int kUcCh = 32, kUcThreads = 128, kUcStage = MVBEV_UPCL_STAGE, kWcPixUp = kWwRows * kWcCols;
 static_assert(kWcCols * 8 == kUcThreads, "thread = (column, channel quad)");
 
-template <int FORM = 3>
+// A lane's channel quad of a source pixel as fp32.  T: the maps' element type — float (one 16-B load), or __half /
+// __bf16 (a bf16 / fp16 autocast backbone's maps: one 8-B load of a 64-B group, half the bytes).  A 16-bit value
+// converts to fp32 exactly and LDS, phase 1 and phase 2 stay fp32, so T is bit for bit the T of the same maps
+// cast to fp32 (tests/test_gpu_half_maps.py).
+// (Keeping the 16-bit values in LDS — boxes of up to 256 pixels in the same 16 KiB, ds_read_b64 taps converted at
+// the read — measured the same: cfg2 bf16 0.2770 vs 0.2775 ms, fp16 0.2818 vs 0.2823, inside the legs' min-max
+// spread, profiles/backbone_dtype_bench.json "warp_ab": not kept.)
+template <typename T>
+__device__ __forceinline__ f32x4a_t cl_quad(const T* p) {
+  if constexpr (std::is_same<T, float>::value) {
+    return *reinterpret_cast<const f32x4a_t*>(p);
+  } else {
+    const uint2 u = *reinterpret_cast<const uint2*>(p);
+    const T* e = reinterpret_cast<const T*>(&u);
+    return f32x4a_t{to_f32<T>(e[0]), to_f32<T>(e[1]), to_f32<T>(e[2]), to_f32<T>(e[3])};
+  }
+}
+
+template <int FORM = 3, typename T = float>
 __global__ __launch_bounds__(kUcThreads) void warp_up_wino_cl_kernel(const UpArgs ua, int r3_rows) {
   __shared__ __attribute__((aligned(16))) f32x4a_t box_px[kUcStage * 8];  // [pixel][quad]
   __shared__ __attribute__((aligned(16))) f32x4a_t pax[kWcPixUp];  // ax0, ax1, ax2, ay0
@@ -427,12 +445,12 @@ __global__ __launch_bounds__(kUcThreads) void warp_up_wino_cl_kernel(const UpArg
   const int R = bxv[1] - br0 + 1, Cb = bxv[3] - bc0 + 1;  // (an all-outside block: R, Cb <= 0)
   const bool staged = bxv[1] >= 0 && R * Cb <= kUcStage;  // uniform per block
   // the batch item's 32-channel group (16-B aligned: host check)
-  const float* gbase = static_cast<const float*>(vw.src) + (int64_t)b * vw.sB + (int64_t)grp * kUcCh;
+  const T* gbase = static_cast<const T*>(vw.src) + (int64_t)b * vw.sB + (int64_t)grp * kUcCh;
   if (staged) {
     for (int it = tid; it < R * Cb * 8; it += kUcThreads) {
       const int px = it >> 3, q = it & 7;
       const int r = px / Cb, c = px - r * Cb;
-      box_px[it] = *reinterpret_cast<const f32x4a_t*>(gbase + (int64_t)(br0 + r) * vw.sH + (int64_t)(bc0 + c) * vw.sW + 4 * q);
+      box_px[it] = cl_quad<T>(gbase + (int64_t)(br0 + r) * vw.sH + (int64_t)(bc0 + c) * vw.sW + 4 * q);
     }
     __syncthreads();
   }
@@ -466,7 +484,7 @@ __global__ __launch_bounds__(kUcThreads) void warp_up_wino_cl_kernel(const UpArg
         for (int r = 0; r < 3; ++r)
 #pragma unroll
           for (int j = 0; j < 3; ++j)
-            s[r][j] = *reinterpret_cast<const f32x4a_t*>(gbase + (int64_t)ro[r] * vw.sH + (int64_t)co[j] * vw.sW + 4 * q);
+            s[r][j] = cl_quad<T>(gbase + (int64_t)ro[r] * vw.sH + (int64_t)co[j] * vw.sW + 4 * q);
       }
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
@@ -572,7 +590,7 @@ __global__ __launch_bounds__(kUcThreads) void up_box_kernel(const UpArgs ua, int
 // Plain fp32 out [B][C][Ho][Wo] at element strides; one thread per output pixel, 8 channels per
 // block; runs only when *gate == gate_tag (the fused warp's report), else exits at once.  Row windows
 // (ABI 11900): dst row v is grid row vw.row0 + v, a.out_rows rows (0 = Ho) — the exact path runs in row
-// bands (bounded memory) and the band exchange's windows.  T: fp32 or fp16 sources (fp32 math).
+// bands (bounded memory) and the band exchange's windows.  T: fp32, fp16 or bf16 sources (fp32 math).
 template <bool UP, typename T>
 __global__ __launch_bounds__(256) void warp_exact_kernel(const UpArgs ua, int pix_blocks, int units) {
   const WarpArgs& a = ua.w;
@@ -644,13 +662,14 @@ __global__ __launch_bounds__(256) void warp_exact_kernel(const UpArgs ua, int pi
 
 }  // namespace mvbev
 
-static int warp_exact(const mvbev_warp_view* views, const int32_t* row0s, int nviews, int src_is_f16, int64_t B,
+static int warp_exact(const mvbev_warp_view* views, const int32_t* row0s, int nviews, int src_kind, int64_t B,
                       int64_t C, int64_t h, int64_t w, int64_t H, int64_t W, int64_t Ho, int64_t Wo, int64_t out_rows,
                       const int32_t* gate, int32_t gate_tag, void* stream) {
   using namespace mvbev;
   if (!views) return MVBEV_ERR_NULL;
   if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || nviews <= 0 || out_rows < 0)
     return MVBEV_ERR_RANK;
+  if (src_kind < 0 || src_kind > 2) return MVBEV_ERR_SHAPE;  // 0 fp32, 1 fp16, 2 bf16
   const int64_t orows = out_rows ? out_rows : Ho;
   if (nviews > kWarpMaxViews || B * nviews > 65535 || C > INT32_MAX || H > INT32_MAX / 2 || W > INT32_MAX / 2 ||
       Ho > INT32_MAX / 2 || orows > Ho || orows * Wo > INT32_MAX - 256 ||
@@ -680,8 +699,10 @@ static int warp_exact(const mvbev_warp_view* views, const int32_t* row0s, int nv
   const bool up = !(h == H && w == W);
 #define MVBEV_EXACT_LAUNCH(UP, T) \
   hipLaunchKernelGGL((warp_exact_kernel<UP, T>), grid, dim3(256), 0, as_stream(stream), ua, pix_blocks, units)
-  if (src_is_f16) {
+  if (src_kind == 1) {
     if (up) MVBEV_EXACT_LAUNCH(true, __half); else MVBEV_EXACT_LAUNCH(false, __half);
+  } else if (src_kind == 2) {
+    if (up) MVBEV_EXACT_LAUNCH(true, __bf16); else MVBEV_EXACT_LAUNCH(false, __bf16);
   } else {
     if (up) MVBEV_EXACT_LAUNCH(true, float); else MVBEV_EXACT_LAUNCH(false, float);
   }
@@ -697,12 +718,12 @@ extern "C" int mvbev_warp_views_exact_f32(const mvbev_warp_view* views, int nvie
 }
 
 extern "C" int mvbev_warp_views_exact_rows(const mvbev_warp_view* views, const int32_t* row0s, int nviews,
-                                           int src_is_f16, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H,
+                                           int src_kind, int64_t B, int64_t C, int64_t h, int64_t w, int64_t H,
                                            int64_t W, int64_t Ho, int64_t Wo, int64_t out_rows,
                                            const int32_t* gate, int32_t gate_tag, void* stream) {
   if (!row0s) return MVBEV_ERR_NULL;
   if (out_rows <= 0) return MVBEV_ERR_RANK;
-  return warp_exact(views, row0s, nviews, src_is_f16, B, C, h, w, H, W, Ho, Wo, out_rows, gate, gate_tag, stream);
+  return warp_exact(views, row0s, nviews, src_kind, B, C, h, w, H, W, Ho, Wo, out_rows, gate, gate_tag, stream);
 }
 
 extern "C" int mvbev_warp_views_upsampled_wino_rows_ex(const mvbev_warp_view* views, int nviews, int64_t B,
@@ -749,9 +770,14 @@ extern "C" int mvbev_warp_views_upsampled_wino_rows_ex(const mvbev_warp_view* vi
                                                        int32_t* nonfinite, int32_t nf_tag, const int32_t* boxes,
                                                        void* stream) {
   using namespace mvbev;
-  if (flags & ~(MVBEV_WARP_DST_ZEROED | MVBEV_WARP_WINO43)) return MVBEV_ERR_SHAPE;
+  if (flags & ~(MVBEV_WARP_DST_ZEROED | MVBEV_WARP_WINO43 | MVBEV_WARP_SRC_F16 | MVBEV_WARP_SRC_BF16))
+    return MVBEV_ERR_SHAPE;
   const bool w43 = (flags & MVBEV_WARP_WINO43) != 0;  // T43: r3_rows counts four-row tiles, 3 per block
   const int form = w43 ? 4 : 3, tpb = w43 ? 3 : 4;
+  // 16-bit maps (channels-last only): 0 fp32, 1 fp16, 2 bf16; both bits: refused
+  const bool f16 = (flags & MVBEV_WARP_SRC_F16) != 0, bf16 = (flags & MVBEV_WARP_SRC_BF16) != 0;
+  if (f16 && bf16) return MVBEV_ERR_SHAPE;
+  const int64_t ea = f16 || bf16 ? 8 : 4;  // elements per 16 B
   if (!views) return MVBEV_ERR_NULL;
   if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || nviews <= 0 || r3_rows <= 0)
     return MVBEV_ERR_RANK;
@@ -784,9 +810,10 @@ extern "C" int mvbev_warp_views_upsampled_wino_rows_ex(const mvbev_warp_view* vi
   bool cl = C % kUcCh == 0 && h < 32768 && w < 16384;  // (the packed window origin of the kernel)
   for (int i = 0; i < nviews; ++i) {
     const WarpView& d = a.v[i];
-    cl = cl && d.sC == 1 && d.sW >= C && d.sH >= d.sW * w && d.sB >= 0 && d.sW % 4 == 0 && d.sH % 4 == 0 &&
-         d.sB % 4 == 0 && (reinterpret_cast<uintptr_t>(d.src) & 15) == 0;
+    cl = cl && d.sC == 1 && d.sW >= C && d.sH >= d.sW * w && d.sB >= 0 && d.sW % ea == 0 && d.sH % ea == 0 &&
+         d.sB % ea == 0 && (reinterpret_cast<uintptr_t>(d.src) & 15) == 0;
   }
+  if ((f16 || bf16) && !cl) return MVBEV_ERR_SHAPE;  // the NCHW form reads fp32 maps
   if (cl) {
     a.tiles_x = (int)ceil_div(Wo, kWcCols);
     a.tiles = a.tiles_x * (int)ceil_div(r3_rows, tpb);
@@ -794,12 +821,19 @@ extern "C" int mvbev_warp_views_upsampled_wino_rows_ex(const mvbev_warp_view* vi
     a.nwg = a.tiles * a.chunks * a.B * a.nviews;
     set_fastdiv(a);
     ua.boxes = boxes;
-    if (w43)
-      hipLaunchKernelGGL((warp_up_wino_cl_kernel<4>), dim3((unsigned)a.nwg), dim3(kUcThreads), 0, as_stream(stream),
-                         ua, (int)r3_rows);
-    else
-      hipLaunchKernelGGL((warp_up_wino_cl_kernel<3>), dim3((unsigned)a.nwg), dim3(kUcThreads), 0, as_stream(stream),
-                         ua, (int)r3_rows);
+#define MVBEV_UPCL_LAUNCH(T)                                                                                        \
+  do {                                                                                                              \
+    if (w43)                                                                                                        \
+      hipLaunchKernelGGL((warp_up_wino_cl_kernel<4, T>), dim3((unsigned)a.nwg), dim3(kUcThreads), 0,               \
+                         as_stream(stream), ua, (int)r3_rows);                                                      \
+    else                                                                                                            \
+      hipLaunchKernelGGL((warp_up_wino_cl_kernel<3, T>), dim3((unsigned)a.nwg), dim3(kUcThreads), 0,               \
+                         as_stream(stream), ua, (int)r3_rows);                                                      \
+  } while (0)
+    if (f16) MVBEV_UPCL_LAUNCH(__half);
+    else if (bf16) MVBEV_UPCL_LAUNCH(__bf16);
+    else MVBEV_UPCL_LAUNCH(float);
+#undef MVBEV_UPCL_LAUNCH
     MVBEV_CHECK_LAUNCH();
     return MVBEV_OK;
   }
@@ -884,16 +918,18 @@ extern "C" int mvbev_warp_views_upsampled(const mvbev_warp_view* views, int nvie
 // tile (pitch 65: conflict-free column reads); reads 256-B channel rows, writes 128-B pixel lines.
 namespace mvbev {
 struct TransArgs {
-  const float* src[kWarpMaxViews];
+  const void* src[kWarpMaxViews];
   int64_t sB[kWarpMaxViews], sC[kWarpMaxViews], sH[kWarpMaxViews], sW[kWarpMaxViews];
-  float* dst[kWarpMaxViews];
+  void* dst[kWarpMaxViews];
   int B, C, H, W, ctiles, ptiles;
 };
-// VEC (every view: contiguous planes, sC / sB / H * W multiples of 4, 16-B aligned, C % 32 == 0):
-// 16-B loads of 4 pixels of a channel and 16-B stores of 4 channels of a pixel
-template <bool VEC>
+// VEC (every view: contiguous planes, sC / sB / H * W multiples of 4, 4-element aligned, C % 32 == 0):
+// one load of 4 pixels of a channel and one store of 4 channels of a pixel (16 B; 8 B for 2-byte elements).
+// E: the element as its bits' size — float, or uint16_t for fp16 / bf16 maps (a plain transposition).
+template <bool VEC, typename E>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const TransArgs a) {
-  __shared__ float t[32][65];
+  typedef E e4_t __attribute__((ext_vector_type(4)));  // 4-element aligned
+  __shared__ E t[32][65 * (4 / sizeof(E))];  // (2-byte elements: pitch 130, the fp32 tile's bank rows)
   const int HW = a.H * a.W;
   int blk = blockIdx.x;
   const int pt = blk % a.ptiles;
@@ -902,14 +938,14 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const TransArgs a) {
   blk /= a.ctiles;
   const int b = blk % a.B, v = blk / a.B;
   const int tid = threadIdx.x;
-  const float* src = a.src[v] + (int64_t)b * a.sB[v];
-  float* dst = a.dst[v] + (int64_t)b * HW * a.C;
+  const E* src = static_cast<const E*>(a.src[v]) + (int64_t)b * a.sB[v];
+  E* dst = static_cast<E*>(a.dst[v]) + (int64_t)b * HW * a.C;
   if constexpr (VEC) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {  // thread = (channel, pixel quad)
       const int cc = (tid >> 4) + 16 * k, pq = tid & 15, p = pt * 64 + 4 * pq;
       if (p < HW) {
-        const f32x4a_t q = *reinterpret_cast<const f32x4a_t*>(src + (int64_t)(ct * 32 + cc) * a.sC[v] + p);
+        const e4_t q = *reinterpret_cast<const e4_t*>(src + (int64_t)(ct * 32 + cc) * a.sC[v] + p);
         t[cc][4 * pq] = q.x;
         t[cc][4 * pq + 1] = q.y;
         t[cc][4 * pq + 2] = q.z;
@@ -921,8 +957,8 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const TransArgs a) {
     for (int k = 0; k < 2; ++k) {  // thread = (pixel, channel quad)
       const int pp = (tid >> 3) + 32 * k, cq = tid & 7, p = pt * 64 + pp;
       if (p < HW)
-        *reinterpret_cast<f32x4a_t*>(dst + (int64_t)p * a.C + ct * 32 + 4 * cq) =
-            f32x4a_t{t[4 * cq][pp], t[4 * cq + 1][pp], t[4 * cq + 2][pp], t[4 * cq + 3][pp]};
+        *reinterpret_cast<e4_t*>(dst + (int64_t)p * a.C + ct * 32 + 4 * cq) =
+            e4_t{t[4 * cq][pp], t[4 * cq + 1][pp], t[4 * cq + 2][pp], t[4 * cq + 3][pp]};
     }
     return;
   }
@@ -941,35 +977,46 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const TransArgs a) {
 }
 }  // namespace mvbev
 
-extern "C" int mvbev_nchw_to_nhwc_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t C, int64_t H,
-                                      int64_t W, void* stream) {
+extern "C" int mvbev_nchw_to_nhwc_ex(const mvbev_warp_view* views, int nviews, int elem_size, int64_t B, int64_t C,
+                                     int64_t H, int64_t W, void* stream) {
   using namespace mvbev;
   if (!views) return MVBEV_ERR_NULL;
   if (nviews <= 0 || B <= 0 || C <= 0 || H <= 0 || W <= 0) return MVBEV_ERR_RANK;
+  if (elem_size != 4 && elem_size != 2) return MVBEV_ERR_SHAPE;
+  const uintptr_t amask = 4 * (uintptr_t)elem_size - 1;  // a 4-element vector's alignment
   if (nviews > kWarpMaxViews || C > INT32_MAX || H * W > INT32_MAX - 64) return MVBEV_ERR_SHAPE;
   TransArgs a = {};
   for (int i = 0; i < nviews; ++i) {
     if (!views[i].src || !views[i].dst) return MVBEV_ERR_NULL;
-    a.src[i] = static_cast<const float*>(views[i].src);
+    a.src[i] = views[i].src;
     a.sB[i] = views[i].src_strides[0];
     a.sC[i] = views[i].src_strides[1];
     a.sH[i] = views[i].src_strides[2];
     a.sW[i] = views[i].src_strides[3];
-    a.dst[i] = static_cast<float*>(views[i].dst);
+    a.dst[i] = views[i].dst;
   }
   a.B = (int)B; a.C = (int)C; a.H = (int)H; a.W = (int)W;
   a.ctiles = (int)ceil_div(C, 32);
   a.ptiles = (int)ceil_div(H * W, 64);
   const int64_t nwg = (int64_t)a.ptiles * a.ctiles * B * nviews;
   if (nwg > INT32_MAX) return MVBEV_ERR_SHAPE;
-  bool vec = C % 32 == 0 && (H * W) % 4 == 0 && (reinterpret_cast<uintptr_t>(views[0].dst) & 15) == 0;
+  bool vec = C % 32 == 0 && (H * W) % 4 == 0;
   for (int i = 0; i < nviews; ++i)
     vec = vec && a.sW[i] == 1 && a.sH[i] == W && a.sC[i] % 4 == 0 && a.sB[i] % 4 == 0 &&
-          (reinterpret_cast<uintptr_t>(a.src[i]) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.dst[i]) & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<true>, dim3((unsigned)nwg), dim3(256), 0, as_stream(stream), a);
-  else
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, as_stream(stream), a);
+          (reinterpret_cast<uintptr_t>(a.src[i]) & amask) == 0 && (reinterpret_cast<uintptr_t>(a.dst[i]) & amask) == 0;
+#define MVBEV_TRANS_LAUNCH(VEC, E) \
+  hipLaunchKernelGGL((nchw_to_nhwc_kernel<VEC, E>), dim3((unsigned)nwg), dim3(256), 0, as_stream(stream), a)
+  if (elem_size == 4) {
+    if (vec) MVBEV_TRANS_LAUNCH(true, float); else MVBEV_TRANS_LAUNCH(false, float);
+  } else {
+    if (vec) MVBEV_TRANS_LAUNCH(true, uint16_t); else MVBEV_TRANS_LAUNCH(false, uint16_t);
+  }
+#undef MVBEV_TRANS_LAUNCH
   MVBEV_CHECK_LAUNCH();
   return MVBEV_OK;
+}
+
+extern "C" int mvbev_nchw_to_nhwc_f32(const mvbev_warp_view* views, int nviews, int64_t B, int64_t C, int64_t H,
+                                      int64_t W, void* stream) {
+  return mvbev_nchw_to_nhwc_ex(views, nviews, 4, B, C, H, W, stream);
 }

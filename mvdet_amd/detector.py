@@ -32,8 +32,18 @@ The library is loaded at construction on a GPU, so a missing build fails there.
 uint8 ``[B,N,H,W,3]`` tensor: the reference's ``train_trans`` (``main.py:38-40``) then runs first as one HIP launch and
 its result is what ``forward`` would have been given.  Any other input takes the path above unchanged; the
 ``state_dict`` does not hold the transform.
+
+``backbone_dtype=`` (``PerspTransDetector`` only; None, ``torch.bfloat16`` or ``torch.float16``; default None: nothing
+changes) runs the backbone halves and the image head's first conv under ``torch.autocast`` in that dtype.  Parameters
+and the ``state_dict`` stay fp32 (the reference's checkpoints load as before).  In inference the 16-bit maps go to the
+fused upsample warp as they come out: it converts each value to fp32 exactly, so the hot path computes what it
+computes from those maps cast to fp32, bit for bit; the rounding to 16 bits is the backbone's.  In training the maps
+are cast to fp32 before the native forward and backward.  There is no loss scaling: fp16 training (a
+``torch.amp.GradScaler``) is the caller's business.
 """
 from __future__ import annotations
+
+import contextlib
 
 import torch
 import torch.nn as nn
@@ -42,6 +52,7 @@ import torch.nn.functional as F
 from . import _native
 from . import autograd as native_autograd
 from . import img_head
+from . import ops
 from .backbone import build_backbone
 from .geometry import coord_map as make_coord_map
 from .geometry import projection_matrices, upsample_shape
@@ -57,6 +68,10 @@ class _ViewsDetector(nn.Module):
     # a ``mvdet_amd.frames.FrameTransform`` (or None): when set, ``forward`` also takes the decoded frames, a uint8
     # ``[B,N,H,W,3]`` tensor, and runs the transform first.  A plain attribute: the ``state_dict`` does not hold it.
     frame_transform = None
+    # None, torch.bfloat16 or torch.float16: the autocast dtype of the backbone halves and the image head's first
+    # conv in ``_views_forward`` (``PerspTransDetector(backbone_dtype=...)`` sets it; the variants leave it None).
+    # A plain attribute: parameters and the ``state_dict`` stay fp32.
+    backbone_dtype = None
 
     def _frames(self, imgs):
         """``imgs`` as ``forward`` takes them: decoded uint8 frames go through ``frame_transform`` (on the module's
@@ -101,19 +116,30 @@ class _ViewsDetector(nn.Module):
 
     def _views_forward(self, imgs: torch.Tensor, visualize: bool = False):
         """The camera loop up to the warp: every view's backbone map (channels-last when the backbone is) and
-        the image head's results (``:62-66``)."""
+        the image head's results (``:62-66``).  With ``backbone_dtype`` the backbone halves and the image head's
+        first conv run under ``torch.autocast`` in that dtype: the maps come out 16-bit (and go on as they come
+        out — whatever dtype arrives is what the engine dispatches on), the head's 64-channel ``g`` is cast to
+        fp32 so that the fused image head still runs."""
         dev = self._device
         imgs_result, low, head_low = [], [], []
         split_head, native_head = self._img_head_splits(), None
+        bdt = self.backbone_dtype
+
+        def cast():  # a fresh context per use: the backbone's autocast, or nothing
+            return torch.autocast("cuda", dtype=bdt) if bdt is not None else contextlib.nullcontext()
         for cam in range(self.num_cam):
             x = imgs[:, cam].to(dev)
-            feat = self.base_pt1(x.contiguous(memory_format=torch.channels_last) if self.channels_last else x)
-            feat = self.base_pt2(feat)
+            with cast():
+                feat = self.base_pt1(x.contiguous(memory_format=torch.channels_last) if self.channels_last else x)
+                feat = self.base_pt2(feat)
             # the image head runs its first 1x1 conv before upsampling (it commutes with the
             # bilinear upsample: per-pixel affine, weights summing to 1) on 64 instead of 512
             # channels
             if split_head:
-                g = self.img_classifier[0](feat)
+                with cast():
+                    g = self.img_classifier[0](feat)
+                if g.dtype in ops.HALF_MAP_DTYPES:
+                    g = g.float()
                 if native_head is None:
                     native_head = self._img_head_native(g)
                 if native_head:
@@ -122,7 +148,8 @@ class _ViewsDetector(nn.Module):
                     imgs_result.append(self.img_classifier[2](
                         F.relu(F.interpolate(g, self.upsample_shape, mode="bilinear"))))
             else:
-                imgs_result.append(self.img_classifier(F.interpolate(feat, self.upsample_shape, mode="bilinear")))
+                imgs_result.append(self.img_classifier(F.interpolate(
+                    feat.float() if feat.dtype in ops.HALF_MAP_DTYPES else feat, self.upsample_shape, mode="bilinear")))
             # the 3x upsample (:65) happens inside the fused warp below (and, training, its
             # adjoint inside the warp adjoint)
             # (a channels-last backbone's maps stay channels-last: the fused warp's line-per-pixel kernel)
@@ -178,9 +205,12 @@ class _ViewsDetector(nn.Module):
 class PerspTransDetector(_ViewsDetector):
     def __init__(self, dataset, arch: str = "resnet18", device=None, precision: str = "bf16x3",
                  wino_conv1: bool = True, wino_conv2: bool = True, channels_last: bool = True,
-                 native_img_head: bool = True, frame_transform=None):
+                 native_img_head: bool = True, frame_transform=None, backbone_dtype=None):
         super().__init__()
+        if backbone_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError(f"backbone_dtype must be None, torch.bfloat16 or torch.float16, not {backbone_dtype!r}")
         self.frame_transform = frame_transform
+        self.backbone_dtype = backbone_dtype
         out_channel = self._init_views(dataset, arch, device, channels_last, native_img_head)
         self.map_classifier = nn.Sequential(nn.Conv2d(out_channel * self.num_cam + 2, 512, 3, padding=1), nn.ReLU(),
                                             nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),
@@ -203,6 +233,9 @@ class PerspTransDetector(_ViewsDetector):
         ws = None if training else self.engine.workspace(B, dev)
         low, imgs_result = self._views_forward(imgs, visualize)
         if training:  # a4-a9 forward and backward on the HIP kernels (autograd.py)
+            # 16-bit maps (backbone_dtype) enter the native forward + backward as fp32: a differentiable cast,
+            # the gradient returns to the backbone in the maps' dtype
+            low = [f.float() if f.dtype in ops.HALF_MAP_DTYPES else f for f in low]
             map_result = native_autograd.project_fuse_backbone(self.engine, low, self.map_classifier)
         else:
             self.engine.warp_views_upsampled(ws, list(range(self.num_cam)), low)  # a4 + a5 + a6

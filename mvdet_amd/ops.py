@@ -25,6 +25,8 @@ from .geometry import kornia_src_norm_from_dst_norm
 
 KC = _native.KC
 BN = _native.BN
+# the 16-bit dtypes of backbone maps the fused upsample warp takes (what bf16 / fp16 autocast emits)
+HALF_MAP_DTYPES = (torch.float16, torch.bfloat16)
 
 
 def _require_cuda(*tensors):
@@ -330,12 +332,17 @@ def _gate(gate):
     return flag.data_ptr(), int(tag)
 
 
+# mvbev_warp_views_exact_rows' src_kind
+_EXACT_SRC_KIND = {torch.float32: _native.EXACT_SRC_F32, torch.float16: _native.EXACT_SRC_F16,
+                   torch.bfloat16: _native.EXACT_SRC_BF16}
+
+
 def warp_views_exact_into(srcs, m_norms, dsts, up_hw=None, gate=None, row0s=None, grid_rows: Optional[int] = None) -> None:
     """The reference's own evaluation order of the warp (a5) — and, with ``up_hw``, of the 3x
     upsample feeding it (a4 + a5): ``mvbev_warp_views_exact_f32``.  Every product
     ``F.interpolate`` and ``grid_sample`` form is formed (zero weights included), so a NaN / inf in
     ``srcs`` reaches exactly the outputs it reaches in ``persp_trans_detector.py:65-69``.  fp32 (or,
-    ABI 11900, fp16) ``srcs[i]`` [B,C,h,w] (the warp's source, or with ``up_hw`` the backbone map),
+    ABI 11900, fp16; or bf16) ``srcs[i]`` [B,C,h,w] (the warp's source, or with ``up_hw`` the backbone map),
     ``dsts[i]`` fp32 [B,C,rows,Wo] views (innermost stride 1); ``gate`` as ``conv3x3_desc``'s (the
     non-finite guard).  ``row0s`` (ABI 11900, ``mvbev_warp_views_exact_rows``): ``dsts[i]`` holds the
     ``rows`` grid rows from ``row0s[i]`` of a ``grid_rows``-row grid (row windows: the exact path in
@@ -354,8 +361,8 @@ def warp_views_exact_into(srcs, m_norms, dsts, up_hw=None, gate=None, row0s=None
     if row0s is None and grid_rows is not None and grid_rows != rows:
         raise ValueError("a row window needs row0s")
     for s_, d in zip(srcs, dsts):
-        if tuple(s_.shape) != (B, C, h, w) or s_.dtype != dtype or dtype not in (torch.float32, torch.float16):
-            raise ValueError("all views must be fp32 (or fp16) [B,C,h,w] of one shape and dtype")
+        if tuple(s_.shape) != (B, C, h, w) or s_.dtype != dtype or dtype not in _EXACT_SRC_KIND:
+            raise ValueError("all views must be fp32 (or fp16 / bf16) [B,C,h,w] of one shape and dtype")
         if tuple(d.shape) != (B, C, rows, Wo) or d.dtype != torch.float32 or d.stride(3) != 1:
             raise ValueError(f"dst must be an fp32 [{B},{C},{rows},{Wo}] view with unit column stride")
     arr = _view_table(srcs, m_norms, dsts)
@@ -366,7 +373,7 @@ def warp_views_exact_into(srcs, m_norms, dsts, up_hw=None, gate=None, row0s=None
         _native.check(st, "mvbev_warp_views_exact_f32")
         return
     r0 = (ctypes.c_int32 * n)(*([0] * n if row0s is None else [int(r) for r in row0s]))
-    st = lib.mvbev_warp_views_exact_rows(arr, r0, n, int(dtype == torch.float16), B, C, h, w, H, W, Ho, Wo, rows,
+    st = lib.mvbev_warp_views_exact_rows(arr, r0, n, _EXACT_SRC_KIND[dtype], B, C, h, w, H, W, Ho, Wo, rows,
                                          gp, gt, _stream(dsts[0]))
     _native.check(st, "mvbev_warp_views_exact_rows")
 
@@ -494,17 +501,22 @@ def mask_gated(mask: torch.Tensor, out: torch.Tensor, gate) -> torch.Tensor:
 
 def is_channels_last_source(x: torch.Tensor) -> bool:
     """True when the fused warps take ``x`` [B,C,H,W] fp32 in their channels-last form (ABI 11700: unit
-    channel stride, whole 32-channel groups, strides multiples of 4 floats, 16-B aligned)."""
+    channel stride, whole 32-channel groups, strides multiples of 4 floats, 16-B aligned).  fp16 / bf16 ``x``
+    (the fused upsample warp alone takes those): the same rule with strides multiples of 8 elements, so that
+    every 32-channel group (64 B) stays 16-B aligned."""
     sB, sC, sH, sW = x.stride()
     C = x.shape[1]
-    return (x.dtype == torch.float32 and C % 32 == 0 and sC == 1 and sW >= C and sH >= sW * x.shape[3]
-            and sW % 4 == 0 and sH % 4 == 0 and sB % 4 == 0 and x.data_ptr() % 16 == 0)
+    if x.dtype not in (torch.float32,) + HALF_MAP_DTYPES:
+        return False
+    ea = 16 // x.element_size()  # elements per 16 B
+    return (C % 32 == 0 and sC == 1 and sW >= C and sH >= sW * x.shape[3]
+            and sW % ea == 0 and sH % ea == 0 and sB % ea == 0 and x.data_ptr() % 16 == 0)
 
 
 def to_channels_last_into(srcs, dsts) -> list:
-    """``mvbev_nchw_to_nhwc_f32``: copy fp32 ``srcs[i]`` [B,C,H,W] (any strides) into the contiguous
-    [B,H,W,C] ``dsts[i]``, every view in one launch; returns the channels-last [B,C,H,W] views of
-    ``dsts`` (the same logical tensors as ``srcs``)."""
+    """``mvbev_nchw_to_nhwc_f32`` / ``_ex``: copy fp32 (or fp16 / bf16) ``srcs[i]`` [B,C,H,W] (any strides)
+    into the contiguous [B,H,W,C] ``dsts[i]`` of the same dtype, every view in one launch; returns the
+    channels-last [B,C,H,W] views of ``dsts`` (the same logical tensors as ``srcs``)."""
     n = len(srcs)
     if n == 0:
         return []
@@ -512,14 +524,19 @@ def to_channels_last_into(srcs, dsts) -> list:
         raise ValueError("need 1..16 matching srcs / dsts")
     _require_cuda(*srcs, *dsts)
     B, C, H, W = srcs[0].shape
+    dtype = srcs[0].dtype
     for s_, d in zip(srcs, dsts):
-        if tuple(s_.shape) != (B, C, H, W) or s_.dtype != torch.float32:
-            raise ValueError("all views must be fp32 [B,C,H,W] of one shape")
-        if tuple(d.shape) != (B, H, W, C) or d.dtype != torch.float32 or not d.is_contiguous():
-            raise ValueError(f"dst must be a contiguous fp32 [{B},{H},{W},{C}] tensor")
+        if tuple(s_.shape) != (B, C, H, W) or s_.dtype != dtype or dtype not in (torch.float32,) + HALF_MAP_DTYPES:
+            raise ValueError("all views must be fp32 (or fp16 / bf16) [B,C,H,W] of one shape and dtype")
+        if tuple(d.shape) != (B, H, W, C) or d.dtype != dtype or not d.is_contiguous():
+            raise ValueError(f"dst must be a contiguous {dtype} [{B},{H},{W},{C}] tensor")
     arr = _view_table(srcs, None, dsts, [(0, 0, 0, 1)] * n)
-    st = _native.load().mvbev_nchw_to_nhwc_f32(arr, n, B, C, H, W, _stream(dsts[0]))
-    _native.check(st, "mvbev_nchw_to_nhwc_f32")
+    if dtype == torch.float32:
+        st = _native.load().mvbev_nchw_to_nhwc_f32(arr, n, B, C, H, W, _stream(dsts[0]))
+        _native.check(st, "mvbev_nchw_to_nhwc_f32")
+    else:
+        st = _native.load().mvbev_nchw_to_nhwc_ex(arr, n, 2, B, C, H, W, _stream(dsts[0]))
+        _native.check(st, "mvbev_nchw_to_nhwc_ex")
     return [d.permute(0, 3, 1, 2) for d in dsts]
 
 
@@ -960,15 +977,21 @@ def warp_views_wino_rows_into(srcs, m_norms, t: torch.Tensor, slots, Cs: int, K:
     if Cs % KC or C > Cs:
         raise ValueError("Cs must be a multiple of 8 holding C")
     dtype = srcs[0].dtype
-    if dtype == torch.float16 and up_hw is not None:
-        raise TypeError("the fused upsample warp takes fp32 backbone maps")
+    if up_hw is not None and dtype in HALF_MAP_DTYPES and not all(is_channels_last_source(s_) for s_ in srcs):
+        raise TypeError("the fused upsample warp takes fp32 backbone maps, or fp16 / bf16 ones that are "
+                        "channels-last sources (is_channels_last_source: unit channel stride, C % 32 == 0, "
+                        "16-B aligned 32-channel groups; to_channels_last_into copies NCHW maps)")
+    if up_hw is None and dtype == torch.bfloat16:
+        raise TypeError("the fused warp of already-upsampled features takes fp32 or fp16 (bf16: backbone-"
+                        "resolution maps with up_hw only)")
     for s_ in srcs:
-        if tuple(s_.shape) != (B, C, H, W) or s_.dtype != dtype or dtype not in (torch.float32, torch.float16):
-            raise ValueError("all views must be fp32 (or fp16: ABI 11900) [B,C,H,W] of one shape and dtype")
+        if tuple(s_.shape) != (B, C, H, W) or s_.dtype != dtype or dtype not in (torch.float32,) + HALF_MAP_DTYPES:
+            raise ValueError("all views must be fp32 (or fp16: ABI 11900; bf16 with up_hw) [B,C,H,W] of one shape "
+                             "and dtype")
     arr = _view_table(srcs, m_norms, [t.data_ptr() + 32 * (int(slot) * (Cs // KC)) * nx * r3 * Wo for slot in slots],
                       [(K8 * nx * r3 * Wo, nx * r3 * Wo, Wo, 1)] * n)  # 32-byte units
     flags = ((_native.WARP_DST_ZEROED if dst_zeroed else 0) | (_native.WARP_SRC_F16 if dtype == torch.float16 else 0)
-             | (_native.WARP_WINO43 if form == 4 else 0))
+             | (_native.WARP_SRC_BF16 if dtype == torch.bfloat16 else 0) | (_native.WARP_WINO43 if form == 4 else 0))
     fp, ft = _gate(nonfinite)
     if boxes is not None:  # (from warp_wino_boxes with the same matrices, in the same view order)
         _require_cuda(boxes)

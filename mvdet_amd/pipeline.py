@@ -366,12 +366,12 @@ class ProjectFuse:
         reference's NaN pattern)."""
         return self.wino_conv1 and self.nonfinite_views(device) == 0
 
-    def _wino_warp_applies(self, ws: Workspace, feats, half_ok: bool = False) -> bool:
+    def _wino_warp_applies(self, ws: Workspace, feats, half_ok: bool = False, dtypes=None) -> bool:
         """The fused warp + B^T applies: inference (or a training forward whose backward reads T, not the
-        slab) over the whole grid, fp32 features (or, ``half_ok``: fp16 ones — config 4; ABI 11900),
-        finite geometry."""
+        slab) over the whole grid, fp32 features (or, ``half_ok``: fp16 ones — config 4; ABI 11900; or the
+        caller's own ``dtypes``), finite geometry."""
         H = self.grid_hw[0]
-        dts = (torch.float32, torch.float16) if half_ok else (torch.float32,)
+        dts = dtypes if dtypes is not None else (torch.float32, torch.float16) if half_ok else (torch.float32,)
         return (self.wino_warp and (not ws.store_y2 or ws.train_t_only) and ws.y1_rows == (0, H) and ws.slab_zeroed
                 and all(f.dtype in dts for f in feats) and len({f.dtype for f in feats}) == 1
                 and self.src_hw[1] >= 2 and self.wino_active(ws.slab.device))
@@ -468,13 +468,24 @@ class ProjectFuse:
     def warp_views_upsampled(self, ws: Workspace, cams: Sequence[int], feats: Sequence[torch.Tensor]) -> None:
         """a4 + a5 fused: ``feats[i]`` is view ``cams[i]``'s
         backbone-resolution map [B,C,h,w]; the 3x bilinear upsample to ``src_hw``
-        (``persp_trans_detector.py:65``) happens inside the warp, never in HBM."""
+        (``persp_trans_detector.py:65``) happens inside the warp, never in HBM.
+
+        fp16 / bf16 maps (a backbone under autocast) stay 16-bit on the fused path when ``C % 32 == 0``: the
+        channels-last kernel loads them as they are (NCHW ones through the 16-bit one-launch copy), converts
+        each value to fp32 exactly and computes what it computes from ``f.float()``, bit for bit; the
+        non-finite guard's exact path reads the same 16-bit maps.  With ``C % 32 != 0`` (or where the fused
+        path does not apply) 16-bit maps are cast once with ``.float()`` and take the fp32 path."""
         for cam, f in zip(cams, feats):
             if f.shape[1] != self.C or f.shape[2] > self.src_hw[0] or f.shape[3] > self.src_hw[1]:
                 raise ValueError(f"view {cam}: features {tuple(f.shape)} cannot upsample to {self.src_hw}")
         self._check_warp_ws(ws)
-        if self._wino_warp_applies(ws, feats) and all(
-                f.shape[3] >= 4 and (f.stride(3) == 1 or ops.is_channels_last_source(f)) for f in feats):
+        half = any(f.dtype in ops.HALF_MAP_DTYPES for f in feats)
+        if half and not (self.C % 32 == 0 and all(f.shape[3] >= 4 for f in feats)
+                         and (self.cl_upsample or all(ops.is_channels_last_source(f) for f in feats))
+                         and self._wino_warp_applies(ws, feats, dtypes=ops.HALF_MAP_DTYPES)):
+            feats, half = [f.float() for f in feats], False  # (one dtype for every view, as the kernels want)
+        if self._wino_warp_applies(ws, feats, dtypes=ops.HALF_MAP_DTYPES if half else None) and all(
+                f.shape[3] >= 4 and (half or f.stride(3) == 1 or ops.is_channels_last_source(f)) for f in feats):
             src = list(feats)
             if self.cl_upsample and self.C % 32 == 0 and not all(ops.is_channels_last_source(f) for f in src):
                 src = self._channels_last_maps(ws, src)
@@ -488,9 +499,10 @@ class ProjectFuse:
     def _channels_last_maps(self, ws: Workspace, feats) -> list:
         """The views' backbone maps copied to channels-last buffers of the workspace (one launch)."""
         B, C, h, w = feats[0].shape
-        shape = (B, h, w, C)
-        if ws.cl_maps is None or len(ws.cl_maps) < len(feats) or tuple(ws.cl_maps[0].shape) != shape:
-            ws.cl_maps = [torch.empty(shape, dtype=torch.float32, device=ws.slab.device)
+        shape, dtype = (B, h, w, C), feats[0].dtype
+        if ws.cl_maps is None or len(ws.cl_maps) < len(feats) or tuple(ws.cl_maps[0].shape) != shape or \
+                ws.cl_maps[0].dtype != dtype:
+            ws.cl_maps = [torch.empty(shape, dtype=dtype, device=ws.slab.device)
                           for _ in range(max(len(feats), self.num_cam))]
         return ops.to_channels_last_into(list(feats), ws.cl_maps[:len(feats)])
 

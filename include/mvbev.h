@@ -1228,6 +1228,43 @@ int mvbev_clear_mod_frames(const void* gt, const void* det, int dtype, const int
                            int32_t* n_gt, int32_t* n_det, int32_t* matched, double* modp_sum, double* cost,
                            int32_t* match, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- the projection on plain channels-last tensors (added after 12500; mvbev_version() stays 12500) ----
+ *
+ * persp_trans_detector.py:65, :69, :77 as one op (mvdet_amd.ProjectViews): every view's map upsampled to H x W
+ * (bilinear, align_corners=False; the identity when h x w == H x W), warped onto the Ho x Wo grid and written into
+ * its channel slice of one channels-last tensor, then the two coord channels.  The upsampled maps are never
+ * written.  Element kinds: 0 = fp32, 1 = fp16, 2 = bf16; all math is fp32, a 16-bit value is converted exactly at
+ * the load and every output value is rounded once (to nearest even) at the store.
+ *
+ * Forward.  views[i].src: [B][h][w][C] as element strides {batch, 1, row, column} (dst and dst_strides are not read),
+ * views[i].m the src_norm <- dst_norm matrix for the H x W source; src_kind the kind of every source.  out:
+ * [B][Ho][Wo][Ctot] dense, of out_kind (src_kind, or 0); view i owns channels [i C, (i + 1) C) of a pixel, the coord
+ * channels (coord_channels != 0: x then y, the values of mvbev_fill_coord_map_f32) nviews C and nviews C + 1; channels
+ * past those, up to Ctot, are not touched.  Coordinates, corners and weights are those of every other warp here
+ * (a non-finite coordinate gives NaN, a sample outside the source 0).  H >= h, W >= w, nviews <= 16, and with
+ * coord channels Ho, Wo >= 2, else MVBEV_ERR_SHAPE.  Loads and stores use the widest of 16, 8 and 4 bytes (or one
+ * element) that the base addresses, the strides, Ctot and C allow; any C >= 1 works.  One launch. */
+int mvbev_project_views_cl_forward(const mvbev_warp_view* views, int nviews, int src_kind, int64_t B, int64_t C,
+                                   int64_t h, int64_t w, int64_t H, int64_t W, int64_t Ho, int64_t Wo, void* out,
+                                   int out_kind, int64_t Ctot, int coord_channels, void* stream);
+/* Backward: the adjoint as a deterministic gather over the views' plans (mvbev_warp_adjoint_plan when h x w ==
+ * H x W, else mvbev_warp_upsampled_adjoint_plan).  grad_out: [B][Ho][Wo][Ctot] dense, of grad_out_kind; view i reads
+ * channels [i C, (i + 1) C).  views[i].grad_src: [B][h][w][C] of grad_src_kind as element strides {batch, 1, row =
+ * w * column, column >= C}; NULL: the view is skipped.  grad_out_kind is grad_src_kind or 0.  Every element of a
+ * grad_src is written: the sum over its pixel's plan row in CSR order, one fp32 fma per entry (the sum and order of
+ * mvbev_warp_views_adjoint with MVBEV_LAYOUT_F32: bitwise its result for fp32), zero for an empty row.  One launch,
+ * no atomics. */
+typedef struct mvbev_project_views_grad {
+  const int32_t* row_ptr;      /* the view's plan */
+  const int32_t* col;
+  const float* val;
+  void* grad_src;
+  int64_t grad_src_strides[4];
+} mvbev_project_views_grad;
+int mvbev_project_views_cl_backward(const void* grad_out, int grad_out_kind, int64_t Ctot,
+                                    const mvbev_project_views_grad* views, int nviews, int grad_src_kind, int64_t B,
+                                    int64_t C, int64_t h, int64_t w, int64_t Ho, int64_t Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,9 @@ Public surface (mirrors the reference's):
 * ``warp_perspective`` — drop-in for kornia 0.6.11
   ``kornia.geometry.transform.warp_perspective`` (default-argument path).
 * ``ProjectFuse`` — the hot path (warp + zero-copy concat + fusion) as an engine.
+* ``ProjectViews`` — the projection alone (upsample, warp, concat, coord channels) as a differentiable op for a
+  head of your own: contiguous fp32 or channels-last fp32 / bf16 / fp16 maps in, the same format out
+  (``mvdet_amd.project_views``).
 * ``postprocess.nms`` / ``threshold_rows`` / ``frame_results`` — drop-ins for
   ``multiview_detector.utils.nms.nms`` and the evaluation rows of ``trainer.py:97-157``.
 * ``GaussianMSE`` / ``detection_loss`` / ``gaussian_kernels`` — drop-ins for
@@ -60,10 +63,13 @@ from . import frames  # noqa: F401
 from .frames import FrameTransform, resize_normalize  # noqa: F401
 from . import evaluation  # noqa: F401
 from .evaluation import DetectionEvaluator, evaluate  # noqa: F401
+from . import project_views  # noqa: F401
+from .project_views import ProjectViews  # noqa: F401
 from .variants import ImageProjVariant, NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
            "detection_loss", "gaussian_kernels", "targets", "PointTargets", "pack_step", "img_head", "upsample_relu_conv1x1",
            "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant",
            "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant", "frames",
-           "FrameTransform", "resize_normalize", "evaluation", "DetectionEvaluator", "evaluate"]
+           "FrameTransform", "resize_normalize", "evaluation", "DetectionEvaluator", "evaluate", "project_views",
+           "ProjectViews"]

@@ -147,7 +147,11 @@ EXPORTS = (
     "mvbev_clear_mod_frames",
     # 16-bit backbone maps on the fused upsample warp (added after 12500; the version stays 12500)
     "mvbev_nchw_to_nhwc_ex",
+    # the projection on plain channels-last tensors (added after 12500; the version stays 12500)
+    "mvbev_project_views_cl_forward",
+    "mvbev_project_views_cl_backward",
 )
+KIND_F32, KIND_F16, KIND_BF16 = 0, 1, 2  # element kinds of mvbev_project_views_cl_*
 CLEAR_MOD_MAX_SMALL, CLEAR_MOD_MAX_LARGE = 1024, 1 << 20  # MVBEV_CLEAR_MOD_MAX_*
 EVAL_F32, EVAL_F64, EVAL_GT_F64_DET_F32 = 0, 1, 2  # MVBEV_EVAL_*
 IMG_PROJ_PER_PIXEL = 1  # MVBEV_IMG_PROJ_PER_PIXEL
@@ -250,6 +254,12 @@ class ImgHeadItem(ctypes.Structure):
 class FrameView(ctypes.Structure):
     """``mvbev_frame_view`` (include/mvbev.h)."""
     _fields_ = [("src", ctypes.c_void_p), ("batch_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64)]
+
+
+class ProjectViewsGrad(ctypes.Structure):
+    """``mvbev_project_views_grad`` (include/mvbev.h)."""
+    _fields_ = [("row_ptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("val", ctypes.c_void_p),
+                ("grad_src", ctypes.c_void_p), ("grad_src_strides", ctypes.c_int64 * 4)]
 
 
 class NativeError(RuntimeError):
@@ -567,6 +577,12 @@ def _declare(lib):
     lib.mvbev_clear_mod_frames.restype = ctypes.c_int
     lib.mvbev_clear_mod_frames.argtypes = ([_p, _p, ctypes.c_int, _p, _p] + [_i64] * 5 + [ctypes.c_double] +
                                            [_p] * 7 + [ctypes.c_size_t, _p])  # outputs, match, workspace, bytes, stream
+    lib.mvbev_project_views_cl_forward.restype = ctypes.c_int
+    lib.mvbev_project_views_cl_forward.argtypes = ([ctypes.POINTER(WarpView), ctypes.c_int, ctypes.c_int] + [_i64] * 8 +
+                                                   [_p, ctypes.c_int, _i64, ctypes.c_int, _p])  # out, kind, Ctot, coord
+    lib.mvbev_project_views_cl_backward.restype = ctypes.c_int
+    lib.mvbev_project_views_cl_backward.argtypes = ([_p, ctypes.c_int, _i64, ctypes.POINTER(ProjectViewsGrad),
+                                                     ctypes.c_int, ctypes.c_int] + [_i64] * 6 + [_p])
 
 
 def load(path: os.PathLike | str | None = None):

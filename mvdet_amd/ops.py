@@ -15,6 +15,7 @@ missing library or a bad argument raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Optional, Sequence, Tuple
 
@@ -244,6 +245,51 @@ def warp_views_into(srcs, m_norms, dsts, split: bool = False, C: Optional[int] =
     _native.check(fn(arr, n, B, C, H, W, Ho, Wo, _stream(dsts[0])), name)
 
 
+# warp_perspective's adjoint plans, one per (normalised matrix, sizes, device), least recently used first: the
+# reference passes the same matrices every step, so a training loop builds each plan once
+_WARP_PLAN_CACHE: "collections.OrderedDict" = collections.OrderedDict()
+_WARP_PLAN_CACHE_SIZE = 64
+
+
+def _warp_plan(m_norm: torch.Tensor, src_hw, grid_hw, device) -> "WarpAdjointPlan":
+    key = (m_norm.numpy().tobytes(), tuple(src_hw), tuple(grid_hw), str(device))
+    plan = _WARP_PLAN_CACHE.get(key)
+    if plan is None:
+        plan = _WARP_PLAN_CACHE[key] = WarpAdjointPlan(m_norm, src_hw, grid_hw, device)
+        while len(_WARP_PLAN_CACHE) > _WARP_PLAN_CACHE_SIZE:
+            _WARP_PLAN_CACHE.popitem(last=False)
+    else:
+        _WARP_PLAN_CACHE.move_to_end(key)
+    return plan
+
+
+class _WarpPerspective(torch.autograd.Function):
+    """``warp_perspective`` for a ``src`` that requires grad: the same forward kernel; backward: the deterministic
+    plan gather (``mvbev_warp_views_adjoint``), one "view" per batch item, from the host matrices of the forward.
+    Saves nothing (the warp is linear in ``src``)."""
+
+    @staticmethod
+    def forward(ctx, src, m_norm, dsize):
+        B, C = src.shape[:2]
+        out = torch.empty((B, C, dsize[0], dsize[1]), dtype=src.dtype, device=src.device)
+        ctx.m_norm, ctx.src_shape, ctx.dsize = m_norm, tuple(src.shape), dsize
+        return warp_into(src.detach(), m_norm.to(src.device).contiguous(), out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        B, C, H, W = ctx.src_shape
+        if grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
+            grad_out = grad_out.to(torch.float32).contiguous()
+        grad_src = torch.empty(ctx.src_shape, dtype=torch.float32, device=grad_out.device)
+        plans = [_warp_plan(ctx.m_norm[b], (H, W), ctx.dsize, grad_out.device) for b in range(B)]
+        for b0 in range(0, B, 16):  # <= 16 views per launch
+            bs = range(b0, min(B, b0 + 16))
+            warp_views_adjoint([grad_out[b:b + 1] for b in bs], [plans[b] for b in bs],
+                               [grad_src[b:b + 1] for b in bs])
+        return grad_src, None, None
+
+
 def warp_perspective(src: torch.Tensor, M: torch.Tensor, dsize: Tuple[int, int], mode: str = "bilinear",
                      padding_mode: str = "zeros", align_corners: bool = True,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -253,6 +299,12 @@ def warp_perspective(src: torch.Tensor, M: torch.Tensor, dsize: Tuple[int, int],
     fp32 exactly as kornia does; the HIP kernel does transform + divide + bilinear
     gather.  Only bilinear / zeros / align_corners=True are implemented (the only
     combination the reference exercises, ``persp_trans_detector.py:69``).
+
+    Under autograd an fp32 ``src`` that requires grad gets its gradient (the same forward kernel and values; the
+    backward is the deterministic gather over adjoint plans cached per matrix, sizes and device).  What has no
+    gradient here raises instead of dropping it: ``M.requires_grad`` (``NotImplementedError``: no gradient to the
+    homography), an fp16 ``src`` that requires grad (``NotImplementedError``) and ``out=`` with a ``src`` that
+    requires grad (``RuntimeError``, as torch's ``out=`` ops).
     """
     if not isinstance(src, torch.Tensor):
         raise TypeError(f"Input src type is not a torch.Tensor. Got {type(src)}")
@@ -268,7 +320,20 @@ def warp_perspective(src: torch.Tensor, M: torch.Tensor, dsize: Tuple[int, int],
     ho, wo = int(dsize[0]), int(dsize[1])
     if M.shape[0] != B:
         raise ValueError(f"M batch {M.shape[0]} != src batch {B}")
-    m_norm = kornia_src_norm_from_dst_norm(M, (H, W), (ho, wo)).to(src.device).contiguous()
+    grad = torch.is_grad_enabled()
+    if grad and M.requires_grad:
+        raise NotImplementedError("warp_perspective has no gradient with respect to the homography M: detach it")
+    if grad and src.requires_grad:
+        if out is not None:
+            raise RuntimeError("warp_perspective(): functions with out=... arguments don't support automatic "
+                               "differentiation, but src requires grad")
+        if src.dtype != torch.float32:
+            raise NotImplementedError(f"warp_perspective's backward takes a float32 src, got {src.dtype}")
+    m_norm = kornia_src_norm_from_dst_norm(M, (H, W), (ho, wo))
+    if grad and src.requires_grad:
+        _require_cuda(src)
+        return _WarpPerspective.apply(src, m_norm, (ho, wo))
+    m_norm = m_norm.to(src.device).contiguous()
     if out is None:
         out = torch.empty((B, C, ho, wo), dtype=src.dtype, device=src.device)
     return warp_into(src, m_norm, out)

@@ -1265,6 +1265,57 @@ int mvbev_project_views_cl_backward(const void* grad_out, int grad_out_kind, int
                                     const mvbev_project_views_grad* views, int nviews, int grad_src_kind, int64_t B,
                                     int64_t C, int64_t h, int64_t w, int64_t Ho, int64_t Wo, void* stream);
 
+/* ---- the weighted multi-plane projection (mvdet_amd.ProjectPlanes; mvbev_version() stays 12500) ----
+ *
+ *   world_v = sum_d warp_{v,d}(upsample(weight_v[:, d] * feat_v)),  world = cat([world_v for v] + [coord_map])
+ *
+ * with the layouts, element kinds, coordinates, taps and rounding of mvbev_project_views_cl_*: the sum over the
+ * nplanes <= 8 planes is taken inside the gather, so neither the products nor the per-plane warps are written.
+ *
+ * Forward.  views[i].feat: [B][h][w][C] of src_kind as element strides {batch, 1, row, column >= C} (one batch
+ * item's map spans < 2^31 elements); views[i].weight: fp32 [B][nplanes][h][w], dense.  mats: DEVICE fp32
+ * [nviews][nplanes][9], plane d of view i's src_norm <- dst_norm matrix for the H x W source (the kernel reads
+ * it; the host does not).  out as mvbev_project_views_cl_forward's.  Per tap the term is (a_t * weight[b][d][q_t]) *
+ * feat[b][q_t][c] with a_t that entry point's tap coefficient, accumulated in fp32 through the planes in order;
+ * with nplanes = 1 and weights of 1.0 the result is bitwise mvbev_project_views_cl_forward's.  A plane whose
+ * coordinates are non-finite makes the pixel NaN; a plane that samples outside the source adds 0.  Ho, Wo >= 2.
+ * One launch. */
+typedef struct mvbev_project_planes_view {
+  const void* feat;
+  int64_t feat_strides[4];
+  const float* weight;
+} mvbev_project_planes_view;
+int mvbev_project_planes_cl_forward(const mvbev_project_planes_view* views, int nviews, int nplanes,
+                                    const float* mats, int src_kind, int64_t B, int64_t C, int64_t h, int64_t w,
+                                    int64_t H, int64_t W, int64_t Ho, int64_t Wo, void* out, int out_kind,
+                                    int64_t Ctot, int coord_channels, void* stream);
+/* Backward, a deterministic gather.  With G_d[c] = sum_e val_e grad_out[b][col_e][i C + c] over row q of plane
+ * d of view i (row_ptr [nplanes][h w + 1] indexing col / val: the planes' plans of mvbev_warp_adjoint_plan /
+ * mvbev_warp_upsampled_adjoint_plan side by side, each row_ptr offset by where its col / val start), one fp32 fma
+ * per entry in CSR order:
+ *   grad_feat[b][q][c] = sum_d weight[b][d][q] G_d[c]   (of map_kind, layout as mvbev_project_views_grad.grad_src;
+ *                                                        fp32 fmas in plane order, rounded once)
+ *   grad_weight[b][d][q] = sum_c feat[b][q][c] G_d[c]   (fp32 [B][nplanes][h][w] dense; per lane over its 16-B
+ *                         channel units in ascending order, then the pixel's 8 lanes by a xor butterfly 1, 2, 4)
+ * grad_feat NULL / grad_weight NULL: that gradient is not computed (weight / feat is then not read and may be
+ * NULL); both NULL: the view is skipped.  feat_strides as grad_feat_strides: {batch, 1, row = w * column,
+ * column >= C}.  grad_out_kind is map_kind or 0.  One launch, no atomics, bitwise repeatable. */
+typedef struct mvbev_project_planes_grad {
+  const int32_t* row_ptr;
+  const int32_t* col;
+  const float* val;
+  const void* feat;
+  int64_t feat_strides[4];
+  const float* weight;
+  void* grad_feat;
+  int64_t grad_feat_strides[4];
+  float* grad_weight;
+} mvbev_project_planes_grad;
+int mvbev_project_planes_cl_backward(const void* grad_out, int grad_out_kind, int64_t Ctot,
+                                     const mvbev_project_planes_grad* views, int nviews, int nplanes, int map_kind,
+                                     int64_t B, int64_t C, int64_t h, int64_t w, int64_t Ho, int64_t Wo,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

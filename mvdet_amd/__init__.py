@@ -9,6 +9,8 @@ Public surface (mirrors the reference's):
 * ``ProjectViews`` — the projection alone (upsample, warp, concat, coord channels) as a differentiable op for a
   head of your own: contiguous fp32 or channels-last fp32 / bf16 / fp16 maps in, the same format out
   (``mvdet_amd.project_views``).
+* ``ProjectPlanes`` — the weighted multi-plane projection: every view through D ground-parallel planes, mixed by a
+  per-pixel weight, summed inside the gather (one launch forward, one backward; ``mvdet_amd.project_planes``).
 * ``postprocess.nms`` / ``threshold_rows`` / ``frame_results`` — drop-ins for
   ``multiview_detector.utils.nms.nms`` and the evaluation rows of ``trainer.py:97-157``.
 * ``GaussianMSE`` / ``detection_loss`` / ``gaussian_kernels`` — drop-ins for
@@ -65,6 +67,8 @@ from . import evaluation  # noqa: F401
 from .evaluation import DetectionEvaluator, evaluate  # noqa: F401
 from . import project_views  # noqa: F401
 from .project_views import ProjectViews  # noqa: F401
+from . import project_planes  # noqa: F401
+from .project_planes import ProjectPlanes  # noqa: F401
 from .variants import ImageProjVariant, NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
@@ -72,4 +76,4 @@ __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess
            "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant",
            "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant", "frames",
            "FrameTransform", "resize_normalize", "evaluation", "DetectionEvaluator", "evaluate", "project_views",
-           "ProjectViews"]
+           "ProjectViews", "project_planes", "ProjectPlanes"]

@@ -150,6 +150,8 @@ EXPORTS = (
     # the projection on plain channels-last tensors (added after 12500; the version stays 12500)
     "mvbev_project_views_cl_forward",
     "mvbev_project_views_cl_backward",
+    "mvbev_project_planes_cl_forward",
+    "mvbev_project_planes_cl_backward",
 )
 KIND_F32, KIND_F16, KIND_BF16 = 0, 1, 2  # element kinds of mvbev_project_views_cl_*
 CLEAR_MOD_MAX_SMALL, CLEAR_MOD_MAX_LARGE = 1024, 1 << 20  # MVBEV_CLEAR_MOD_MAX_*
@@ -260,6 +262,19 @@ class ProjectViewsGrad(ctypes.Structure):
     """``mvbev_project_views_grad`` (include/mvbev.h)."""
     _fields_ = [("row_ptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("val", ctypes.c_void_p),
                 ("grad_src", ctypes.c_void_p), ("grad_src_strides", ctypes.c_int64 * 4)]
+
+
+class ProjectPlanesView(ctypes.Structure):
+    """``mvbev_project_planes_view`` (include/mvbev.h)."""
+    _fields_ = [("feat", ctypes.c_void_p), ("feat_strides", ctypes.c_int64 * 4), ("weight", ctypes.c_void_p)]
+
+
+class ProjectPlanesGrad(ctypes.Structure):
+    """``mvbev_project_planes_grad`` (include/mvbev.h)."""
+    _fields_ = [("row_ptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("val", ctypes.c_void_p),
+                ("feat", ctypes.c_void_p), ("feat_strides", ctypes.c_int64 * 4), ("weight", ctypes.c_void_p),
+                ("grad_feat", ctypes.c_void_p), ("grad_feat_strides", ctypes.c_int64 * 4),
+                ("grad_weight", ctypes.c_void_p)]
 
 
 class NativeError(RuntimeError):
@@ -583,6 +598,13 @@ def _declare(lib):
     lib.mvbev_project_views_cl_backward.restype = ctypes.c_int
     lib.mvbev_project_views_cl_backward.argtypes = ([_p, ctypes.c_int, _i64, ctypes.POINTER(ProjectViewsGrad),
                                                      ctypes.c_int, ctypes.c_int] + [_i64] * 6 + [_p])
+    lib.mvbev_project_planes_cl_forward.restype = ctypes.c_int
+    lib.mvbev_project_planes_cl_forward.argtypes = ([ctypes.POINTER(ProjectPlanesView), ctypes.c_int, ctypes.c_int, _p,
+                                                     ctypes.c_int] + [_i64] * 8 +  # views, N, D, mats, kind, sizes
+                                                    [_p, ctypes.c_int, _i64, ctypes.c_int, _p])
+    lib.mvbev_project_planes_cl_backward.restype = ctypes.c_int
+    lib.mvbev_project_planes_cl_backward.argtypes = ([_p, ctypes.c_int, _i64, ctypes.POINTER(ProjectPlanesGrad),
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_i64] * 6 + [_p])
 
 
 def load(path: os.PathLike | str | None = None):

@@ -49,6 +49,32 @@ def projection_matrices(dataset) -> List[torch.Tensor]:
     return [torch.from_numpy(map_zoom_mat @ i2w[cam] @ img_zoom_mat) for cam in range(dataset.num_cam)]
 
 
+def plane_projection_matrices(dataset, heights) -> List[List[torch.Tensor]]:
+    """``projection_matrices`` for the planes z = ``heights[d]`` (the dataset's world units) instead of the ground
+    plane alone: per camera a list of D float64 matrices (upsampled-image pixels -> grid pixels of plane d).  A world
+    point (X, Y, z) projects to ``K @ ([r1 r2 r3 t] @ [X Y z 1]^T) = K @ [r1, r2, z r3 + t] @ [X Y 1]^T``, so the
+    chain is ``projection_matrices``' with ``np.delete(extrinsic, 2, 1)`` replaced by those columns; z = 0 gives
+    ``projection_matrices`` exactly."""
+    base = dataset.base
+    ups = upsample_shape(dataset.img_shape, dataset.img_reduce)
+    img_reduce = np.array(dataset.img_shape) / np.array(ups)
+    img_zoom_mat = np.diag(np.append(img_reduce, [1]))
+    map_zoom_mat = np.diag(np.append(np.ones([2]) / dataset.grid_reduce, [1]))
+    out = []
+    for cam in range(dataset.num_cam):
+        ext = np.asarray(base.extrinsic_matrices[cam])
+        planes = []
+        for z in heights:
+            cols = np.delete(ext, 2, 1)  # [r1 r2 t]
+            if float(z) != 0.0:
+                cols[:, 2] = float(z) * ext[:, 2] + ext[:, 3]
+            worldgrid2imgcoord = base.intrinsic_matrices[cam] @ cols @ base.worldgrid2worldcoord_mat
+            planes.append(torch.from_numpy(map_zoom_mat @ (PERMUTATION @ np.linalg.inv(worldgrid2imgcoord))
+                                           @ img_zoom_mat))
+        out.append(planes)
+    return out
+
+
 def coord_map(ho: int, wo: int) -> torch.Tensor:
     """``create_coord_map([ho, wo, 1])`` → [1, 2, ho, wo] fp32 (x, y in [-1, 1])."""
     grid_x, grid_y = np.meshgrid(np.arange(wo), np.arange(ho))

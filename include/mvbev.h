@@ -1316,6 +1316,38 @@ int mvbev_project_planes_cl_backward(const void* grad_out, int grad_out_kind, in
                                      int64_t B, int64_t C, int64_t h, int64_t w, int64_t Ho, int64_t Wo,
                                      void* stream);
 
+/* ---- the inference residual tail (added after 12500; mvbev_version() stays 12500) ----
+ *
+ * mvdet_amd.ResidualTail runs ResNet-18's layer4 (resnet.py:43-75) in eval mode with BatchNorm folded into the
+ * 3x3 convs, which are mvbev_conv3x3_bf16x3_ex on MVBEV_LAYOUT_SPLIT_BF16 in and out.  These are the layout and
+ * epilogue passes between the fp32 channels-last maps of the backbone and that layout.  All are element-wise over
+ * (pixel, 8-channel group) units of 32 B, one launch, no atomics.  C % 8 == 0; M = nviews * B items, item
+ * v * B + b = batch item b of view v.
+ *
+ * Polyphase form of a split-bf16 tensor [M][C/8][h][w]: [4 M][C/8][h2][w2] with h2 = ceil(h / 2), w2 = ceil(w / 2),
+ * item 4 m + 2 p + q holding x_pq[r][c] = x[m][2 r + p][2 c + q] and exact zeros where 2 r + p >= h or
+ * 2 c + q >= w.  A dilation-4 3x3 conv (padding 4) of x is the dilation-2 conv (padding 2) of each sub-grid on its
+ * own: the taps of output (2 r + p, 2 c + q) are x[2 (r + 2 i) + p][2 (c + 2 j) + q], i, j in {-1, 0, 1}, the zero
+ * padding included.
+ *
+ * mvbev_cl_to_split_bf16: views[i].src = [B][h][w][C] of src_kind (0 fp32, 1 fp16, 2 bf16) as element strides
+ * {batch, 1, row, column >= C}, 16-B aligned with strides that keep every 8-channel unit 16-B aligned (dst and m
+ * of the table are not read); dst: the plain (polyphase == 0) or polyphase layout, hi = bf16(x) to nearest even,
+ * lo = bf16(x - hi).  Every unit of dst is written, the zero pads included. */
+int mvbev_cl_to_split_bf16(const mvbev_warp_view* views, int nviews, int src_kind, int64_t B, int64_t C, int64_t h,
+                           int64_t w, int polyphase, void* dst, void* stream);
+/* out = relu(y + identity), the close of a residual block: y split-bf16, plain or (y_polyphase != 0) polyphase,
+ * read as hi + lo in fp32; identity an fp32 table as above (one view with B = M for a single tensor); out fp32
+ * [M][h][w][C] dense.  ReLU keeps NaN and is torch's otherwise (clamp_min(0)).  next (optional): the same values
+ * split as by mvbev_cl_to_split_bf16 of out, plain or (next_polyphase != 0) polyphase with its zero pads — the next
+ * block's conv input without a conversion launch. */
+int mvbev_res_close_f32(const void* y, int y_polyphase, const mvbev_warp_view* identity, int nviews, int64_t B,
+                        int64_t C, int64_t h, int64_t w, float* out, void* next, int next_polyphase, void* stream);
+/* The polyphase layout [4 M][C/8][h2][w2] back to the plain [M][C/8][h][w] (a dilation-4 conv's output for the
+ * dilation-1 conv after it): a permutation copy of the units; the pads are not read. */
+int mvbev_split_polyphase_to_plain(const void* src, int64_t M, int64_t C, int64_t h, int64_t w, void* dst,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,9 @@ Public surface (mirrors the reference's):
   (``CLEAR_MOD_HUN``, ``evaluateDetection_py``): MODA, MODP, precision and recall with the Hungarian matching of
   all frames in one launch; ``DetectionEvaluator`` — a test epoch from output maps to the four numbers with
   no host sync per frame (``mvdet_amd.evaluation``).
+* ``ResidualTail`` — ResNet-18's layer4 (``base_pt2``) for inference: eval-mode BatchNorm folded into the convs, the
+  3x3 convs on the 3xbf16 kernels over all views at once, fp32-class accuracy (``mvdet_amd.res_tail``;
+  ``PerspTransDetector(native_tail=True)``, off by default).
 
 The compute runs in ``mvdet_amd/lib/libmvbev.so`` (HIP, gfx950; C ABI in
 ``include/mvbev.h``); there is no CPU fallback.
@@ -69,6 +72,8 @@ from . import project_views  # noqa: F401
 from .project_views import ProjectViews  # noqa: F401
 from . import project_planes  # noqa: F401
 from .project_planes import ProjectPlanes  # noqa: F401
+from . import res_tail  # noqa: F401
+from .res_tail import ResidualTail  # noqa: F401
 from .variants import ImageProjVariant, NoJointConvVariant, ResProjVariant  # noqa: F401
 
 __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess", "loss", "GaussianMSE",
@@ -76,4 +81,4 @@ __all__ = ["PerspTransDetector", "warp_perspective", "ProjectFuse", "postprocess
            "sum_head", "ProjectSumHead", "NoJointConvVariant", "thin_fuse", "ProjectThinFuse", "ResProjVariant",
            "img_proj", "ImageProjection", "dense_head", "DenseFuseHead", "ImageProjVariant", "frames",
            "FrameTransform", "resize_normalize", "evaluation", "DetectionEvaluator", "evaluate", "project_views",
-           "ProjectViews", "project_planes", "ProjectPlanes"]
+           "ProjectViews", "project_planes", "ProjectPlanes", "res_tail", "ResidualTail"]

@@ -152,6 +152,10 @@ EXPORTS = (
     "mvbev_project_views_cl_backward",
     "mvbev_project_planes_cl_forward",
     "mvbev_project_planes_cl_backward",
+    # the inference residual tail (added after 12500; the version stays 12500)
+    "mvbev_cl_to_split_bf16",
+    "mvbev_res_close_f32",
+    "mvbev_split_polyphase_to_plain",
 )
 KIND_F32, KIND_F16, KIND_BF16 = 0, 1, 2  # element kinds of mvbev_project_views_cl_*
 CLEAR_MOD_MAX_SMALL, CLEAR_MOD_MAX_LARGE = 1024, 1 << 20  # MVBEV_CLEAR_MOD_MAX_*
@@ -605,6 +609,14 @@ def _declare(lib):
     lib.mvbev_project_planes_cl_backward.restype = ctypes.c_int
     lib.mvbev_project_planes_cl_backward.argtypes = ([_p, ctypes.c_int, _i64, ctypes.POINTER(ProjectPlanesGrad),
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_i64] * 6 + [_p])
+    lib.mvbev_cl_to_split_bf16.restype = ctypes.c_int
+    lib.mvbev_cl_to_split_bf16.argtypes = ([ctypes.POINTER(WarpView), ctypes.c_int, ctypes.c_int] + [_i64] * 4 +
+                                           [ctypes.c_int, _p, _p])  # polyphase, dst, stream
+    lib.mvbev_res_close_f32.restype = ctypes.c_int
+    lib.mvbev_res_close_f32.argtypes = ([_p, ctypes.c_int, ctypes.POINTER(WarpView), ctypes.c_int] + [_i64] * 4 +
+                                        [_p, _p, ctypes.c_int, _p])  # out, next, next_polyphase, stream
+    lib.mvbev_split_polyphase_to_plain.restype = ctypes.c_int
+    lib.mvbev_split_polyphase_to_plain.argtypes = [_p] + [_i64] * 4 + [_p, _p]
 
 
 def load(path: os.PathLike | str | None = None):

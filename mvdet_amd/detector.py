@@ -40,6 +40,13 @@ fused upsample warp as they come out: it converts each value to fp32 exactly, so
 computes from those maps cast to fp32, bit for bit; the rounding to 16 bits is the backbone's.  In training the maps
 are cast to fp32 before the native forward and backward.  There is no loss scaling: fp16 training (a
 ``torch.amp.GradScaler``) is the caller's business.
+
+``native_tail=`` (``PerspTransDetector`` with ``arch="resnet18"`` only; default False: nothing changes) runs
+``base_pt2`` — ResNet-18's layer4, about 72 % of the backbone's arithmetic — in inference as
+``res_tail.ResidualTail``: eval-mode BatchNorm folded into the convs, the four 3x3 convs on the 3xbf16 kernels over
+all views at once, fp32-class accuracy (unlike ``backbone_dtype``, with which it cannot be combined).  ``base_pt1``
+still runs per camera.  With autograd, BatchNorm in train mode or blocks the kernels do not take, the torch modules
+run as without the flag.  The ``state_dict`` is unchanged.
 """
 from __future__ import annotations
 
@@ -53,6 +60,7 @@ from . import _native
 from . import autograd as native_autograd
 from . import img_head
 from . import ops
+from . import res_tail
 from .backbone import build_backbone
 from .geometry import coord_map as make_coord_map
 from .geometry import projection_matrices, upsample_shape
@@ -72,6 +80,22 @@ class _ViewsDetector(nn.Module):
     # conv in ``_views_forward`` (``PerspTransDetector(backbone_dtype=...)`` sets it; the variants leave it None).
     # A plain attribute: parameters and the ``state_dict`` stay fp32.
     backbone_dtype = None
+    # True: in inference ``base_pt2`` (ResNet-18's layer4) runs as ``res_tail.ResidualTail`` over all views at once,
+    # eval-mode BatchNorm folded into the 3xbf16 convs (``PerspTransDetector(native_tail=True)`` sets it; the
+    # variants leave it False).  A plain attribute; where the native path does not apply the torch modules run.
+    native_tail = False
+    _tail = None  # the ResidualTail of base_pt2[0], made on first use (not a module: nothing joins the state_dict)
+
+    def _native_tail(self):
+        """The ``ResidualTail`` when this forward runs ``base_pt2`` natively, else None: the flag is on, the
+        module is on a GPU, ``base_pt2`` is one ``Sequential`` of blocks, no autograd is needed and every
+        BatchNorm of the blocks is in eval mode (the shape is checked by the tail itself)."""
+        if not self.native_tail or self._device.type != "cuda" or self.backbone_dtype is not None or \
+                len(self.base_pt2) != 1 or not isinstance(self.base_pt2[0], nn.Sequential):
+            return None
+        if self._tail is None or self._tail.blocks is not self.base_pt2[0]:
+            self._tail = res_tail.ResidualTail(self.base_pt2[0])
+        return self._tail
 
     def _frames(self, imgs):
         """``imgs`` as ``forward`` takes them: decoded uint8 frames go through ``frame_transform`` (on the module's
@@ -127,11 +151,19 @@ class _ViewsDetector(nn.Module):
 
         def cast():  # a fresh context per use: the backbone's autocast, or nothing
             return torch.autocast("cuda", dtype=bdt) if bdt is not None else contextlib.nullcontext()
-        for cam in range(self.num_cam):
+        def front(cam):  # one camera's frames through the first backbone half
             x = imgs[:, cam].to(dev)
-            with cast():
-                feat = self.base_pt1(x.contiguous(memory_format=torch.channels_last) if self.channels_last else x)
-                feat = self.base_pt2(feat)
+            return self.base_pt1(x.contiguous(memory_format=torch.channels_last) if self.channels_last else x)
+        feats, tail = None, self._native_tail()
+        if tail is not None:  # base_pt1 per camera as below, then the tail once over all views
+            mids = [front(cam) for cam in range(self.num_cam)]
+            feats = tail(mids)  # (the torch blocks per view where the native path does not apply)
+        for cam in range(self.num_cam):
+            if feats is not None:
+                feat = feats[cam]
+            else:
+                with cast():
+                    feat = self.base_pt2(front(cam))
             # the image head runs its first 1x1 conv before upsampling (it commutes with the
             # bilinear upsample: per-pixel affine, weights summing to 1) on 64 instead of 512
             # channels
@@ -205,12 +237,17 @@ class _ViewsDetector(nn.Module):
 class PerspTransDetector(_ViewsDetector):
     def __init__(self, dataset, arch: str = "resnet18", device=None, precision: str = "bf16x3",
                  wino_conv1: bool = True, wino_conv2: bool = True, channels_last: bool = True,
-                 native_img_head: bool = True, frame_transform=None, backbone_dtype=None):
+                 native_img_head: bool = True, frame_transform=None, backbone_dtype=None, native_tail: bool = False):
         super().__init__()
         if backbone_dtype not in (None, torch.bfloat16, torch.float16):
             raise ValueError(f"backbone_dtype must be None, torch.bfloat16 or torch.float16, not {backbone_dtype!r}")
+        if native_tail and arch != "resnet18":
+            raise ValueError(f"native_tail runs ResNet-18's layer4; arch={arch!r} has no residual tail")
+        if native_tail and backbone_dtype is not None:
+            raise ValueError("native_tail takes the fp32 backbone: it cannot be combined with backbone_dtype")
         self.frame_transform = frame_transform
         self.backbone_dtype = backbone_dtype
+        self.native_tail = bool(native_tail)
         out_channel = self._init_views(dataset, arch, device, channels_last, native_img_head)
         self.map_classifier = nn.Sequential(nn.Conv2d(out_channel * self.num_cam + 2, 512, 3, padding=1), nn.ReLU(),
                                             nn.Conv2d(512, 512, 3, padding=2, dilation=2), nn.ReLU(),

@@ -606,6 +606,113 @@ def to_channels_last_into(srcs, dsts) -> list:
 
 
 # ----------------------------------------------------------------------------------------------
+# the inference residual tail's layout and epilogue passes (res_tail.hip)
+
+_SPLIT_SRC_KIND = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def polyphase_hw(h: int, w: int) -> Tuple[int, int]:
+    """Size of the four 2 x 2 polyphase sub-grids of an h x w map (odd sizes padded with zeros)."""
+    return (h + 1) // 2, (w + 1) // 2
+
+
+def split_polyphase_shape(M: int, C: int, h: int, w: int) -> Tuple[int, ...]:
+    """Shape of [M, C, h, w] in the polyphase split-bf16 layout: item 4 m + 2 p + q holds x[m, :, p::2, q::2]."""
+    return split_shape(4 * M, C, *polyphase_hw(h, w))
+
+
+def _cl_table(xs, what: str):
+    """The ``mvbev_warp_view`` table of channels-last ``xs`` ([B,C,h,w] of one shape and dtype, unit channel stride,
+    16-B aligned 8-channel units) and (n, B, C, h, w)."""
+    n = len(xs)
+    if not 0 < n <= 16:
+        raise ValueError(f"{what}: need 1..16 tensors")
+    _require_cuda(*xs)
+    B, C, h, w = xs[0].shape
+    ea = 16 // xs[0].element_size()
+    for x in xs:
+        if tuple(x.shape) != (B, C, h, w) or x.dtype != xs[0].dtype or x.device != xs[0].device:
+            raise ValueError(f"{what}: all tensors must be [B,C,h,w] of one shape, dtype and device")
+        sB, sC, sH, sW = x.stride()
+        if C % KC or (sC != 1 and C != 1) or sW < C or any(s % ea for s in (sB, sH, sW)) or x.data_ptr() % 16:
+            raise ValueError(f"{what}: needs channels-last tensors with C % {KC} == 0 and 16-byte aligned pixels, got "
+                             f"shape {tuple(x.shape)} strides {x.stride()}")
+    return _view_table(xs, None), n, B, C, h, w
+
+
+def channels_last_to_split(xs, polyphase: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mvbev_cl_to_split_bf16``: the channels-last fp32 / fp16 / bf16 ``xs`` (a list of [B,C,h,w], C % 8 == 0) as one
+    split-bf16 blocked tensor of M = len(xs) * B items (item v * B + b), ``split_shape(M, C, h, w)``, or with
+    ``polyphase`` ``split_polyphase_shape(M, C, h, w)``: the 2 x 2 sub-grids on which a dilation-4 conv is a
+    dilation-2 conv.  hi = bf16(x) to nearest even, lo = bf16(x - hi); every element of ``out`` is written (the
+    polyphase zero pads too).  One launch, no ``torch.cat``."""
+    arr, n, B, C, h, w = _cl_table(xs, "channels_last_to_split")
+    if xs[0].dtype not in _SPLIT_SRC_KIND:
+        raise TypeError(f"unsupported dtype {xs[0].dtype}")
+    shape = split_polyphase_shape(n * B, C, h, w) if polyphase else split_shape(n * B, C, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=xs[0].device)
+    elif tuple(out.shape) != shape or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != xs[0].device:
+        raise ValueError(f"out must be a contiguous bf16 {shape} tensor on {xs[0].device}")
+    st = _native.load().mvbev_cl_to_split_bf16(arr, n, _SPLIT_SRC_KIND[xs[0].dtype], B, C, h, w, int(bool(polyphase)),
+                                               out.data_ptr(), _stream(out))
+    _native.check(st, "mvbev_cl_to_split_bf16")
+    return out
+
+
+def residual_close(y: torch.Tensor, identity, hw, y_polyphase: bool = False, next_polyphase: Optional[bool] = None,
+                   next_out: Optional[torch.Tensor] = None):
+    """``mvbev_res_close_f32``: ``relu(y + identity)`` of a residual block.  ``y``: a conv's split-bf16 output for
+    the ``hw`` = (h, w) grid, plain or (``y_polyphase``) polyphase; ``identity``: an fp32 channels-last [M,C,h,w]
+    tensor or a list of per-view [B,C,h,w].  Returns ``(out, next)``: ``out`` fp32 [M,C,h,w] channels-last, and,
+    when ``next_polyphase`` is not None, ``next`` = ``channels_last_to_split([out], next_polyphase)`` bitwise,
+    written by the same launch (into ``next_out`` when given)."""
+    ids = [identity] if isinstance(identity, torch.Tensor) else list(identity)
+    arr, n, B, C, h, w = _cl_table(ids, "residual_close")
+    if ids[0].dtype != torch.float32:
+        raise TypeError("identity must be fp32")
+    _require_cuda(y)
+    if (h, w) != tuple(hw):
+        raise ValueError(f"identity is {h} x {w}, hw says {tuple(hw)}")
+    M = n * B
+    yshape = split_polyphase_shape(M, C, h, w) if y_polyphase else split_shape(M, C, h, w)
+    if tuple(y.shape) != yshape or y.dtype != torch.bfloat16 or not y.is_contiguous() or y.device != ids[0].device:
+        raise ValueError(f"y must be a contiguous bf16 {yshape} tensor on {ids[0].device}")
+    out = torch.empty((M, h, w, C), dtype=torch.float32, device=y.device)
+    nxt = None
+    if next_polyphase is not None:
+        nshape = split_polyphase_shape(M, C, h, w) if next_polyphase else split_shape(M, C, h, w)
+        nxt = next_out if next_out is not None else torch.empty(nshape, dtype=torch.bfloat16, device=y.device)
+        if tuple(nxt.shape) != nshape or nxt.dtype != torch.bfloat16 or not nxt.is_contiguous() or \
+                nxt.device != y.device:
+            raise ValueError(f"next_out must be a contiguous bf16 {nshape} tensor on {y.device}")
+    st = _native.load().mvbev_res_close_f32(y.data_ptr(), int(bool(y_polyphase)), arr, n, B, C, h, w, out.data_ptr(),
+                                            None if nxt is None else nxt.data_ptr(), int(bool(next_polyphase)),
+                                            _stream(y))
+    _native.check(st, "mvbev_res_close_f32")
+    return out.permute(0, 3, 1, 2), nxt
+
+
+def split_polyphase_to_plain(y: torch.Tensor, hw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mvbev_split_polyphase_to_plain``: the polyphase split-bf16 ``y`` ([4 M, C/8, h2, w2, 2, 8]) of an (h, w)
+    grid as the plain ``split_shape(M, C, h, w)`` (the pads are dropped)."""
+    _require_cuda(y)
+    h, w = (int(v) for v in hw)
+    if y.dim() != 6 or y.dtype != torch.bfloat16 or not y.is_contiguous() or y.shape[0] % 4 or \
+            tuple(y.shape) != split_polyphase_shape(y.shape[0] // 4, y.shape[1] * KC, h, w):
+        raise ValueError(f"y must be a contiguous polyphase split-bf16 tensor of a {h} x {w} grid, got {tuple(y.shape)}")
+    M, C = y.shape[0] // 4, y.shape[1] * KC
+    shape = split_shape(M, C, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=y.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != y.device:
+        raise ValueError(f"out must be a contiguous bf16 {shape} tensor on {y.device}")
+    st = _native.load().mvbev_split_polyphase_to_plain(y.data_ptr(), M, C, h, w, out.data_ptr(), _stream(y))
+    _native.check(st, "mvbev_split_polyphase_to_plain")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # convs
 
 def padded_channels(cin: int) -> int:
